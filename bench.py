@@ -6,10 +6,14 @@ PageRank, d = 0.85, 10 iterations, fp64, on SYN-8_5 -- the seeded stand-in for d
 (no network for the real dataset): undirected R-MAT (a,b,c,d) = (0.57,0.19,0.19,0.05), scale 23,
 edgefactor 40, seed 85, duplicates and self-loops removed, vertex ids randomly permuted
 (8.4 M vertices, 628 M stored entries).  One "step" = one complete PageRank run (init + 10 pull
-iterations) with the graph resident in HBM.  At N = 1 the line also carries `secondary`: the
-same measurement on SYN-7_5 (configs[1]'s datagen-7_5-fb stand-in, scale 20, ef 32, seed 75).
+iterations) with the graph resident in HBM.  A plain run sets up, warms up, times the K steps
+and prints the line; --full adds every leg that takes runs of its own (roofline.traffic and
+stream_copy_gbs, processing_ms, cpu_baseline, the parity fields and, at N = 1, `secondary`: the
+same measurement on SYN-7_5, configs[1]'s datagen-7_5-fb stand-in, scale 20, ef 32, seed 75);
+their fields are null without it.  --dump-outputs DIR writes what the last timed step returned
+as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds can be compared.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--graph SYN-7_5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--graph SYN-7_5] [--full] [--dump-outputs DIR]
 
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL): the pull matrix is
 row-partitioned and the rank vector is all-gathered every iteration (strong scaling on the
@@ -66,7 +70,36 @@ def parse():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--partitioned", action="store_true",
                     help="run --algorithm through the multi-GPU (vertex-range) path even at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="PR: beside the headline, everything that takes runs of its own -- the rocprofv3 traffic "
+                         "passes, the stream-copy bandwidth, the executables' processing time, the CPU baseline, "
+                         "parity against the oracle and the SYN-7_5 secondary (their fields are null without it); "
+                         "an --algorithm line is complete either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; a "
+                         "fixed seeded sample of an output larger than the cap, see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 32 << 20   # all files of one --dump-outputs together
+DUMP_SEED = 0
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """--dump-outputs: each array the timed path returned in its last step, as DIR/<name>.npy in
+    float64 (integer labels and levels are exact below 2^53; BFS's unreached marker rounds to
+    2^63).  An array over its share of DUMP_CAP_BYTES is cut to a sample at sorted positions drawn
+    by default_rng(DUMP_SEED) from its size alone, so two runs with the same arguments write the
+    same positions."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).ravel()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(dirpath, f"{name}.npy"), a)
 
 
 # SURVEY.md 8d synthetic stand-ins (no network for the Graphalytics datasets)
@@ -334,6 +367,8 @@ def run_algorithm(args):
         "cpu_baseline": cpu, "parity_vs_oracle": parity, "first_call_ms": first_ms, "split_n1": split,
         "wall_ms_per_call_incl_d2h": wall * 1e3 / args.steps, "graph_gen_s": t_gen,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {alg: out})
     print(json.dumps(line), flush=True)
     G.close()
     ctx.close()
@@ -536,6 +571,8 @@ def run_algorithm_distributed(args):
             "roofline": None, "cpu_baseline": None, "parity_vs_oracle": parity,
             "note": "wall time per call incl. per-round host syncs; the single-GPU path is bench.py --algorithm X",
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {alg: res})
         print(json.dumps(line), flush=True)
     G.close()
     ctx.close()
@@ -784,13 +821,18 @@ def main():
     # a real (non-null) stream: libgx launches on it and RCCL orders against it
     stream = torch.cuda.Stream(device)
     torch.cuda.set_stream(stream)
-    m = measure_pr(csr, args, ctx, device, stream, world, rank, dist, collect=True)
+    # a plain run: set up, warm up, time the steps, dump, print; every other leg needs --full
+    full = args.full and not args.pmc_child
+    collect = bool(args.dump_outputs) or (full and not args.no_cpu_baseline)
+    m = measure_pr(csr, args, ctx, device, stream, world, rank, dist, collect=collect)
     elapsed = m["elapsed"]
     edges_total = nnz * args.iters * args.steps
     value = edges_total / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pagerank": m["result"]})
     traffic, traffic_src = None, None
-    if world == 1 and not args.pmc_child:
+    if world == 1 and full:
         if args.pmc_traffic == "run":
             traffic, traffic_src = measure_pr_traffic(gname)
             if traffic is None:   # e.g. no profiler access: the committed pass, labelled as such
@@ -799,14 +841,14 @@ def main():
                 traffic_src = f"profiles/pmc_pr_pull.json (committed; the in-run passes: {why})"
         else:
             traffic, traffic_src = pmc_traffic(workload), "profiles/pmc_pr_pull.json (committed)"
-    copy_gbs = stream_copy_gbs(device) if rank == 0 and not args.pmc_child else None
+    copy_gbs = stream_copy_gbs(device) if rank == 0 and full else None
 
     exe = None
     secondary = None
     cpu = None
     parity = None
     ref = None
-    if rank == 0 and world == 1 and not args.pmc_child:
+    if rank == 0 and world == 1 and full:
         exe, exe_r = exe_path_pr(csr, args, ctx)
         if not args.no_cpu_baseline:
             from oracle import oracle as O
@@ -843,7 +885,7 @@ def main():
                          # bin/exe/pr's processing time on this graph too
                          "processing": exe_path_pr(csr2, args, ctx)[0]}
 
-    if rank == 0 and not args.no_cpu_baseline and not args.pmc_child:
+    if rank == 0 and not args.no_cpu_baseline and full:
         # the last timed step's scores (gathered from every rank at N > 1) against the fp64 oracle
         from oracle import oracle as O
         if ref is None:

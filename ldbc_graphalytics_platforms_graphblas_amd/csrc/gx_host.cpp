@@ -391,16 +391,32 @@ extern "C" int gx_rmat_csr(int scale, int edgefactor, double a, double b, double
     }
     const uint64_t me = m * mult;
 
-    // counting sort by source (self-loops dropped)
+    // counting sort by source (self-loops dropped).  Every thread owns a range of sources and
+    // scans all edges for them, so no two threads touch the same row; the order of a row's
+    // entries is free, the rows are sorted next.
     std::vector<uint64_t> rp(n + 1, 0);
-    for (uint64_t e = 0; e < me; e++)
-        if (src[e] != dst[e]) rp[src[e] + 1]++;
+    #pragma omp parallel
+    {
+        const uint64_t nt = (uint64_t)omp_get_num_threads(), t = (uint64_t)omp_get_thread_num();
+        const uint32_t lo = (uint32_t)(n * t / nt), hi = (uint32_t)(n * (t + 1) / nt);
+        for (uint64_t e = 0; e < me; e++) {
+            const uint32_t s = src[e];
+            if (s >= lo && s < hi && s != dst[e]) rp[(uint64_t)s + 1]++;
+        }
+    }
     for (uint64_t i = 0; i < n; i++) rp[i + 1] += rp[i];
     std::vector<uint32_t> col(rp[n]);
     {
         std::vector<uint64_t> cur(rp.begin(), rp.end() - 1);
-        for (uint64_t e = 0; e < me; e++)
-            if (src[e] != dst[e]) col[cur[src[e]]++] = dst[e];
+        #pragma omp parallel
+        {
+            const uint64_t nt = (uint64_t)omp_get_num_threads(), t = (uint64_t)omp_get_thread_num();
+            const uint32_t lo = (uint32_t)(n * t / nt), hi = (uint32_t)(n * (t + 1) / nt);
+            for (uint64_t e = 0; e < me; e++) {
+                const uint32_t s = src[e];
+                if (s >= lo && s < hi && s != dst[e]) col[cur[s]++] = dst[e];
+            }
+        }
     }
     std::vector<uint32_t>().swap(src);
     std::vector<uint32_t>().swap(dst);

@@ -28,29 +28,62 @@ import numpy as np
 from .graphio import CSR
 
 
+def _host_threads() -> int:
+    """Threads for host-side numpy work: OMP_NUM_THREADS if set, else the CPUs this process may
+    run on; at most 16."""
+    import os
+    try:
+        t = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        t = 0
+    if t <= 0:
+        t = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    return max(1, min(16, t))
+
+
 def relabel(csr: CSR, order: np.ndarray):
     """Relabel a CSR by `order` (new id -> old id): row order[i] becomes row i, every column
     is renamed, and every row is sorted by new column id (neighbouring lanes of a gather then
     often share an x cache line).  Returns (perm, CSR) with perm[old] = new."""
     n = csr.n
-    deg = np.diff(csr.rowptr.astype(np.int64))
+    rp = csr.rowptr.astype(np.int64)
     perm = np.empty(n, dtype=np.int64)
     perm[order] = np.arange(n, dtype=np.int64)
-    new_deg = deg[order]
+    new_deg = np.diff(rp)[order]
     nrp = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(new_deg, out=nrp[1:])
-    idx = np.repeat(csr.rowptr.astype(np.int64)[order] - nrp[:-1], new_deg) + np.arange(int(nrp[-1]))
-    nci = perm[csr.colidx.astype(np.int64)[idx]]
-    rows = np.repeat(np.arange(n, dtype=np.int64), new_deg)
-    if csr.vals is None:
-        key = np.sort(rows * n + nci)
-        nci = (key - rows * n).astype(np.uint64)
-        vals = None
+    nnz = int(nrp[-1])
+    start = rp[order] - nrp[:-1]   # old position - new position of a row's entries
+    nci = np.empty(nnz, dtype=np.uint64)
+    vals = None if csr.vals is None else np.empty(nnz, dtype=csr.vals.dtype)
+
+    def rows_range(r0: int, r1: int) -> None:
+        # rows [r0, r1) of the result; a row's entries depend on no other row's
+        z0, z1 = int(nrp[r0]), int(nrp[r1])
+        d = new_deg[r0:r1]
+        idx = np.repeat(start[r0:r1], d) + np.arange(z0, z1)
+        c = perm[csr.colidx[idx].astype(np.int64)]
+        rows = np.repeat(np.arange(r0, r1, dtype=np.int64), d)
+        if vals is None:
+            key = np.sort(rows * n + c)
+            nci[z0:z1] = key - rows * n
+        else:
+            o = np.argsort(rows * n + c, kind="stable")
+            nci[z0:z1] = c[o]
+            vals[z0:z1] = csr.vals[idx][o]
+
+    # ranges of ~equal entries, one task each: numpy's sort and gathers release the GIL
+    workers = _host_threads() if nnz >= (1 << 22) else 1
+    cuts = np.unique(np.searchsorted(nrp, np.linspace(0, nnz, 4 * workers + 1).astype(np.int64), side="left"))
+    cuts = np.unique(np.concatenate(([0], cuts, [n])))
+    if workers == 1:
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            rows_range(int(a), int(b))
     else:
-        o = np.argsort(rows * n + nci, kind="stable")
-        nci = nci[o].astype(np.uint64)
-        vals = np.ascontiguousarray(csr.vals[idx][o])
-    return perm, CSR(n, nrp.astype(np.uint64), np.ascontiguousarray(nci), vals)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(workers) as pool:
+            list(pool.map(lambda ab: rows_range(int(ab[0]), int(ab[1])), zip(cuts[:-1], cuts[1:])))
+    return perm, CSR(n, nrp.astype(np.uint64), nci, vals)
 
 
 def hub_relabel(csr: CSR):

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for k in $(seq 1 "$N"); do
   for cfg in "$@"; do
     name=${cfg%%:*}; envs=${cfg#*:}
-    env $(echo "$envs" | tr ',' ' ') timeout -k 10 300 python bench.py --graph "$G" --no-secondary --cpu-seconds 0.1 \
+    env $(echo "$envs" | tr ',' ' ') timeout -k 10 300 python bench.py --full --graph "$G" --no-secondary --cpu-seconds 0.1 \
         --steps 10 --warmup 2 > "$OUT/${G}_${name}_$k.json" 2> "$OUT/${G}_${name}_$k.err" || exit 1
     python3 -c "
 import json; d=json.loads(open('$OUT/${G}_${name}_$k.json').read().strip().splitlines()[-1]); r=d['roofline']
