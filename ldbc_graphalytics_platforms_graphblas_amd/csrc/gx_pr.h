@@ -64,6 +64,8 @@ struct RowBlock {
 // The block's column-sorted prefix of dense columns is stored as narrow 2-byte codes (nbeg,
 // nsg: the block's first code in PrPart::npk and its 512-code supergroups); [lo, hi) is the
 // wide 4-byte remainder.  Unit j of k takes narrow rounds j, j + k, ... as well.
+// Before the narrow codes, the block's pair prefix (pbeg, psg: its first slot in PrPart::ppk and
+// its 256-slot supergroups), in rounds dealt to the units the same way.
 struct SortedUnit {
     int64_t lo;
     int64_t hi;
@@ -78,6 +80,9 @@ struct SortedUnit {
     int32_t seg;        // the block's fields (RowBlock), so a workgroup's first loads are
     int64_t z0, z1;     //   independent: its block's entries [z0, z1), rows [r0, r1), first
     int32_t r0, r1;     //   supergroup seg
+    int64_t pbeg;       // first pair slot of the block (a multiple of 256)
+    int32_t psg;        // pair supergroups (256 slots each) of the block
+    int32_t pad;
 };
 
 // A row stripe of a multi-unit block, combined by k_pr_combine after the units' launch
@@ -145,6 +150,14 @@ struct PrPart {
     uint64_t nnarrow = 0;        // narrow entries (without the delta-only fillers)
     uint64_t ncodes = 0;         // narrow codes, fillers and padding included
     uint32_t null_sg = 0;        // an all-padding supergroup gathering x's zero slot
+    // pair slots (gx_pr_sorted.hip gather_pairs): two entries of one 16-byte aligned pair of x
+    // (columns 2p, 2p + 1) per 4-byte slot, per block a 256-aligned run before its narrow codes
+    DBuf<uint32_t> ppk;
+    DBuf<uint32_t> pbase;        // per pair supergroup: the pair index before its first slot
+    uint64_t npair = 0;          // entries held in pair slots
+    uint64_t npfill = 0;         // filler halves of the slots (odd column pairs, steps above 3)
+    uint64_t npslots = 0;        // slots, fillers and padding included
+    uint32_t pnull_sg = 0;       // an all-padding pair supergroup (the pair of x's zero slot)
     int sorted_nnz = 65536;      // entries per block
     int sorted_rows = 4096;      // rows per block (LDS accumulators)
     int64_t unit_nnz = 0;        // target entries per unit

@@ -18,6 +18,10 @@
 // entry, like the CSR column index.  Inside every full 64-entry group the entries are then
 // permuted (k_sorted_laneperm) so that each LDS-add instruction hits distinct banks; the
 // group's column set, hence its gathers' lines, is unchanged.
+// A block's column-sorted entries are then recoded from the front: its pair prefix as 4-byte
+// slots of two entries of one 16-byte pair of x (ppk / pbase, gather_pairs: one 16-B x load per
+// two entries), the dense columns after it as 2-byte narrow codes (npk / nbase, gather_narrow);
+// spk / gbase / sci serve the wide remainder (gather_units).
 // Gathered values are added into LDS row accumulators (ds_add_f64) in wave-arrival order:
 // scores agree with the row-order sum to ~1e-15 relative but are not bit-reproducible run to
 // run (the parity bar is 1e-12 relative, tests/test_gpu_parity.py).
@@ -50,6 +54,7 @@ constexpr int kCombRows = (1 << kRowBits) / kBS;   // rows per thread in a slab 
 constexpr int kU = 8;            // entries per lane and round (two 16-B index loads)
 constexpr int kRound = kBS * kU; // entries of one round of a workgroup
 constexpr int kNSg = 512;        // codes of a narrow supergroup: one wave's 16-B load per lane
+constexpr int kPSg = 256;        // slots of a pair supergroup: one wave's 16-B load per lane
 constexpr int kJunkRow = (1 << kRowBits) - kWave;   // accumulators [16320, 16384) absorb fillers
 constexpr int kMaxBlockRows = kJunkRow;             // rows of a sorted block
 static_assert(kMaxBlockRows == kPlanBlockRows, "gx_pr.h block rows");
@@ -89,6 +94,9 @@ struct SortedArgs {
     const uint32_t *nbase;   // per narrow supergroup: the column before its first code
     uint32_t null_sg;        // all-padding supergroup (base = zero_col)
     uint32_t nt_col;         // CP bit 2: narrow supergroups from this column on gathered non-temporally
+    const uint32_t *ppk;     // pair slots
+    const uint32_t *pbase;   // per pair supergroup: the pair index before its first slot
+    uint32_t pnull_sg;       // all-padding pair supergroup (base = the pair of zero_col)
     double *xd;              // x of the rows past `live` (store_x, gx_pr.h)
     int64_t live;
     // paced sweep (PrPart::pace)
@@ -257,7 +265,9 @@ __device__ __forceinline__ void long_segment(const SortedArgs &a, const RowBlock
 // with the run's value handed on by ds_bpermute (correct results); 16 = the product kernel
 // under the probes' launch (no queue), the baseline for 12-15; 17 the wide entries (gather_units:
 // 4-byte packed entries and escapes) load and decode but do not gather (narrow unchanged), 18 no
-// wide entries at all (gather_units skipped): the wide tail's share of the launch (round 6).
+// wide entries at all (gather_units skipped): the wide tail's share of the launch (round 6);
+// 19 (gather_narrow only) four 16-B loads per lane and round at the aligned column pairs of
+// entries 0, 2, 4, 6, each feeding two adds (the ceiling of the pair slots, gather_pairs).
 template <int PROBE, int CP>   // CP bit 0: index loads non-temporal (bit 2: gather_narrow)
 __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock &b, int64_t lo64, int64_t hi64,
                                              double *acc, int64_t step64, int32_t k0 = 0, int32_t k1 = 0x7fffffff) {
@@ -510,6 +520,19 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
 #pragma unroll
             for (int k = 0; k < kU; k++) t.g[k] = (k & 3) == 0 ? A.x : (k & 3) == 1 ? A.y : (k & 3) == 2 ? B.x : B.y;
             (void)b0;
+        } else if constexpr (PROBE == 19) {
+            // four 16-B loads per lane at the aligned pairs of columns 0, 2, 4, 6, each feeding two
+            // adds: half the gather instructions on the same lines, the ceiling of the pair slots
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            const d2 *x2 = reinterpret_cast<const d2 *>(a.x_in);
+            const bool ntl = (CP & 4) && b0 >= a.nt_col;
+#pragma unroll
+            for (int k = 0; k < kU; k += 2) {
+                const d2 *xp = x2 + (col[k] >> 1);
+                const d2 v = ntl ? __builtin_nontemporal_load(xp) : *xp;
+                t.g[k] = v.x;
+                t.g[k + 1] = v.y;
+            }
         } else if constexpr (PROBE == 2 || PROBE == 3 || PROBE == 5 || PROBE == 11 || PROBE == 4 || PROBE == 8 || PROBE == 9 ||
                       PROBE == 12) {
 #pragma unroll
@@ -576,6 +599,112 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
         add(tA);
     }
     if constexpr (PROBE == 1 || PROBE == 3 || PROBE == 11) atomicAdd(&acc[threadIdx.x], rsum);
+}
+
+// The pair prefix of a block: 4-byte slots of two entries whose columns lie in one 16-byte
+// aligned pair of x (columns 2p and 2p + 1), so one 16-B load per lane serves two entries:
+//     step << 30 | (selA << 14 | rowA) << 15 | (selB << 14 | rowB)
+// step = the pair index step from the previous slot (0..3; a larger one is split by filler slots
+// of step 3 with two junk rows), sel = the column's low bit, row = the row in the block.  A column
+// pair holding an odd number of the prefix's entries ends in a slot whose second half is a junk
+// row.  A pair supergroup of 256 slots is one wave-load of 16 B per lane (lane l: slots l + 64 k,
+// stored lane-major), decoded by one packed DPP scan; rounds, null supergroup and pipeline as in
+// gather_narrow.  x_in must be 16-byte aligned and the chunk even (pr_plan_sorted, pr_step_sorted).
+template <int CP>
+__device__ __forceinline__ void gather_pairs(const SortedArgs &a, const SortedUnit &u, double *acc) {
+    constexpr int W = kBS / kWave;   // supergroups per round
+    constexpr int kS = kU / 2;       // slots per lane and round
+    const int32_t nrounds = (u.psg + W - 1) / W;
+    if (u.unit >= nrounds) return;
+    const int32_t nr = (nrounds - u.unit + u.nunits - 1) / u.nunits;
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = tid >> 6;
+    const uint32_t sg0 = (uint32_t)(u.pbeg / kPSg);
+    const char *xb = reinterpret_cast<const char *>(a.x_in);
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 16-B aligned (256-slot runs)
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    struct Rd {
+        u32x4 q;
+        uint32_t base;
+    };
+    struct Gt {
+        d2 g[kS];
+        uint32_t r[kS];   // the slot's two (sel, row) halves
+    };
+    auto load = [&](Rd &d, int32_t i) {
+        const int32_t sg = (u.unit + i * u.nunits) * W + wave;
+        const uint32_t g = sg < u.psg ? sg0 + (uint32_t)sg : a.pnull_sg;
+        const u32x4 *qa = reinterpret_cast<const u32x4 *>(a.ppk + (size_t)g * kPSg) + lane;
+        d.q = (CP & 1) ? __builtin_nontemporal_load(qa) : *qa;
+        d.base = a.pbase[g];
+    };
+    // Lane l holds slots l + 64 k (k < 4), so instruction k gathers 64 consecutive slots; the four
+    // lane scans run packed in one register (a field's sum is at most 64 x 3).
+    auto issue = [&](const Rd &d, Gt &t) {
+        const uint32_t w[kS] = {d.q.x, d.q.y, d.q.z, d.q.w};
+        uint32_t pk = 0u;
+#pragma unroll
+        for (int k = 0; k < kS; k++) {
+            pk |= (w[k] >> 30) << (8 * k);
+            t.r[k] = w[k] & 0x3fffffffu;
+            asm volatile("" : "+v"(t.r[k]));
+        }
+        const uint32_t sc = wave_scan_incl(pk);
+        const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)sc, kWave - 1);
+        uint32_t bk = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.base);
+        const uint32_t b0 = bk;
+        uint32_t pr[kS];
+#pragma unroll
+        for (int k = 0; k < kS; k++) {
+            pr[k] = bk + ((sc >> (8 * k)) & 255u);
+            bk += (tot >> (8 * k)) & 255u;
+        }
+        if ((CP & 4) && 2u * b0 >= a.nt_col) {   // past the hub lines: streamed (GX_PR_CP bit 2)
+#pragma unroll
+            for (int k = 0; k < kS; k++) t.g[k] = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(xb + (pr[k] << 4)));
+        } else {
+#pragma unroll
+            for (int k = 0; k < kS; k++) t.g[k] = *reinterpret_cast<const d2 *>(xb + (pr[k] << 4));
+        }
+    };
+    auto add = [&](const Gt &t) {
+#pragma unroll
+        for (int k = 0; k < kS; k++) {
+            const uint32_t r = t.r[k];
+            atomicAdd(&acc[(r >> 15) & ((1u << kRowBits) - 1)], (r & (1u << 29)) ? t.g[k].y : t.g[k].x);
+            atomicAdd(&acc[r & ((1u << kRowBits) - 1)], (r & (1u << kRowBits)) ? t.g[k].y : t.g[k].x);
+        }
+    };
+    Rd dA, dB;
+    Gt tA, tB;
+    load(dA, 0);
+    load(dB, 1);
+    issue(dA, tA);
+    __builtin_amdgcn_sched_barrier(0);
+    load(dA, 2);
+    int32_t k = 1;
+    for (; k + 1 < nr; k += 2) {
+        __builtin_amdgcn_sched_barrier(0);
+        issue(dB, tB);
+        __builtin_amdgcn_sched_barrier(0);
+        load(dB, k + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        add(tA);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(dA, tA);
+        __builtin_amdgcn_sched_barrier(0);
+        load(dA, k + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        add(tB);
+    }
+    if (k < nr) {
+        issue(dB, tB);
+        add(tA);
+        add(tB);
+    } else {
+        add(tA);
+    }
 }
 
 // Paced sweep (PrPart::pace): the CU slot of this workgroup inside its XCD (SE, SH, CU ids of
@@ -663,6 +792,7 @@ __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w,
             __syncthreads();
             if (tid == 0) *reinterpret_cast<volatile uint32_t *>(slot) = 0u;   // this CU's sweep is over
         } else if constexpr (PROBE != 10) {   // probe 10: no entries at all (the fixed costs)
+            gather_pairs<CP>(a, u, acc);   // (no paced form: a paced plan has no pair prefix)
             gather_narrow<CP, PROBE>(a, u, acc);
             if constexpr (PROBE != 18) gather_units<PROBE, CP>(a, b, u.lo, u.hi, acc, u.step);
         }
@@ -1061,19 +1191,21 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(v), kWave - 1);
 }
 
-// D_g of every 256-entry supergroup of every sorted block (grid.y = block), one wave each.
+// D_g of every 256-entry supergroup of every sorted block (grid.y = block) from the end of its
+// pair prefix qsplit[block] on (the narrow codes start afresh there), one wave each.
 __global__ __launch_bounds__(256) void k_narrow_cost(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
-                                                     uint32_t *__restrict__ fill) {
+                                                     const uint32_t *__restrict__ qsplit, uint32_t *__restrict__ fill) {
     const RowBlock b = blocks[blockIdx.y];
     const int64_t z0 = b.nz_begin, N = b.nz_end - z0, ng = (N + 255) >> 8;
+    const int64_t Q = qsplit[blockIdx.y], zq = z0 + (Q << 8);
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
-    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < ng; g += waves) {
+    for (int64_t g = Q + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < ng; g += waves) {
         uint32_t d = 0, st;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int64_t e = (g << 8) + 4 * lane + j;
-            if (e < N) d += narrow_fillers(sci, z0, z0 + e, &st);
+            if (e < N) d += narrow_fillers(sci, zq, z0 + e, &st);
         }
         d = wave_total(d);
         if (lane == 0) fill[b.seg + g] = d;
@@ -1081,9 +1213,14 @@ __global__ __launch_bounds__(256) void k_narrow_cost(const RowBlock *__restrict_
 }
 
 // Per block (one 1024-thread workgroup): the narrow prefix P (supergroups) maximising
-// sum_{g<P} (n_g - D_g) (0 when `enable` is off), the code offset of every supergroup inside
-// the block's narrow run (exclusive prefix of n_g + D_g), and the block's code count.
+// sum_{Q<=g<P} (n_g - D_g) (Q when `enable` is off; Q = qsplit[block], the end of the pair
+// prefix, or 0 when qsplit is null), the code offset of every supergroup inside the block's
+// narrow run (exclusive prefix of n_g + D_g), and the block's code count.
+// The pair prefix is chosen by the same kernel (k_pair_cost's counts): `codes` then holds the
+// slots of each supergroup (null: n_g + D_g) and a filler weighs w4 / 4 entries (narrow: 4).
 __global__ __launch_bounds__(1024) void k_narrow_split(const RowBlock *__restrict__ blocks, const uint32_t *__restrict__ fill,
+                                                       const uint32_t *__restrict__ codes, int w4,
+                                                       const uint32_t *__restrict__ qsplit,
                                                        int enable, int64_t min_entries, uint32_t *__restrict__ nsplit,
                                                        uint32_t *__restrict__ ncode,
                                                        uint32_t *__restrict__ noff) {
@@ -1094,11 +1231,16 @@ __global__ __launch_bounds__(1024) void k_narrow_split(const RowBlock *__restric
     const int64_t N = b.nz_end - b.nz_begin, ng = (N + 255) >> 8;
     const int t = threadIdx.x;
     const int64_t per = (ng + 1023) / 1024, g0 = min(ng, t * per), g1 = min(ng, g0 + per);
+    const int64_t Q = qsplit ? (int64_t)qsplit[blockIdx.x] : 0;
     auto cnt = [&](int64_t g) { return min<int64_t>(256, N - (g << 8)); };
+    auto benefit = [&](int64_t g) { return g < Q ? 0 : 4 * cnt(g) - (int64_t)w4 * (int64_t)fill[b.seg + g]; };
+    auto ncodes = [&](int64_t g) {
+        return g < Q ? 0 : codes ? (int64_t)codes[b.seg + g] : cnt(g) + (int64_t)fill[b.seg + g];
+    };
     int64_t ben = 0, cod = 0;
     for (int64_t g = g0; g < g1; g++) {
-        ben += cnt(g) - (int64_t)fill[b.seg + g];
-        cod += cnt(g) + (int64_t)fill[b.seg + g];
+        ben += benefit(g);
+        cod += ncodes(g);
     }
     sben[t] = ben;
     scod[t] = cod;
@@ -1112,11 +1254,11 @@ __global__ __launch_bounds__(1024) void k_narrow_split(const RowBlock *__restric
     }
     int64_t pb = sben[t] - ben, pc = scod[t] - cod;
     int64_t bv = 0;
-    int32_t bi = 0;   // P = 0 is always allowed
+    int32_t bi = (int32_t)Q;   // P = Q (no code) is always allowed
     for (int64_t g = g0; g < g1; g++) {
         noff[b.seg + g] = (uint32_t)pc;
-        pb += cnt(g) - (int64_t)fill[b.seg + g];
-        pc += cnt(g) + (int64_t)fill[b.seg + g];
+        pb += benefit(g);
+        pc += ncodes(g);
         if (pb > bv) {
             bv = pb;
             bi = (int32_t)(g + 1);
@@ -1137,10 +1279,10 @@ __global__ __launch_bounds__(1024) void k_narrow_split(const RowBlock *__restric
         __syncthreads();
     }
     if (t == 0) {
-        const int32_t P = (enable && N >= min_entries) ? besti[0] : 0;
+        const int32_t P = (enable && N >= min_entries) ? besti[0] : (int32_t)Q;
         nsplit[blockIdx.x] = (uint32_t)P;
         // codes of the prefix: the offset of supergroup P, or all of them
-        ncode[blockIdx.x] = P == 0 ? 0u : (uint32_t)(P < ng ? noff[b.seg + P] : (uint32_t)scod[1023]);
+        ncode[blockIdx.x] = P == Q ? 0u : (uint32_t)(P < ng ? noff[b.seg + P] : (uint32_t)scod[1023]);
     }
 }
 
@@ -1157,22 +1299,24 @@ __global__ void k_narrow_fill(uint16_t *__restrict__ npk, uint64_t ncodes, uint3
 // lane's exclusive scan of code counts.  Whoever emits the last code of a 512-code supergroup
 // stores the next one's base (the column reached); the block's first base is its first column.
 __global__ __launch_bounds__(256) void k_narrow_emit(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
-                                                     const uint32_t *__restrict__ spk, const uint32_t *__restrict__ nsplit,
+                                                     const uint32_t *__restrict__ spk, const uint32_t *__restrict__ qsplit,
+                                                     const uint32_t *__restrict__ nsplit,
                                                      const uint32_t *__restrict__ ncode, const uint32_t *__restrict__ noff,
                                                      const int64_t *__restrict__ nbeg, uint16_t *__restrict__ npk,
                                                      uint32_t *__restrict__ nbase) {
     const RowBlock b = blocks[blockIdx.y];
     const int64_t z0 = b.nz_begin, N = b.nz_end - z0, P = nsplit[blockIdx.y];
+    const int64_t Q = qsplit[blockIdx.y], zq = z0 + (Q << 8);   // the narrow codes follow the pair prefix
     const int64_t nb = nbeg[blockIdx.y], C = ncode[blockIdx.y];
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
-    if (P > 0 && blockIdx.x == 0 && threadIdx.x == 0) nbase[nb / kNSg] = (uint32_t)sci[z0];
-    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < P; g += waves) {
+    if (P > Q && blockIdx.x == 0 && threadIdx.x == 0) nbase[nb / kNSg] = (uint32_t)sci[zq];
+    for (int64_t g = Q + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < P; g += waves) {
         uint32_t fl[4], st[4], n = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int64_t e = (g << 8) + 4 * lane + j;
-            fl[j] = e < N ? narrow_fillers(sci, z0, z0 + e, &st[j]) : 0u;
+            fl[j] = e < N ? narrow_fillers(sci, zq, z0 + e, &st[j]) : 0u;
             n += e < N ? fl[j] + 1 : 0u;
         }
         int64_t pos = nb + noff[b.seg + g] + (wave_scan_incl(n) - n);   // absolute code index
@@ -1194,6 +1338,168 @@ __global__ __launch_bounds__(256) void k_narrow_emit(const RowBlock *__restrict_
                 put(3u, (uint32_t)(kJunkRow + (pos & (kWave - 1))), at);   // the lane's own junk row
             }
             put(c - at, spk[z0 + e] & ((1u << kRowBits) - 1), c);
+        }
+    }
+}
+
+// ---- pair slots (gather_pairs).  The first Q 256-entry supergroups of a block's column-sorted
+// entries are recoded in slots of two entries of one column pair (columns 2p, 2p + 1).  The
+// entries of a pair are consecutive (a run); entry k of its run leads a slot when k is even and
+// takes entry k + 1 as the slot's second half, or a junk row when the run (or the prefix) ends
+// there.  A run whose pair lies more than 3 pairs past the previous run's is preceded by
+// ceil(step / 3) - 1 filler slots.  So the slots of a supergroup do not depend on Q; only whether
+// the slot led by the prefix's last entry has a second half does.
+
+// The lane's four entries 4 lane .. 4 lane + 3 of supergroup g of a block (z0, N entries, the
+// first Nq of them in the prefix), one wave per supergroup.
+struct PairLane {
+    uint32_t pair[4], col[4], next[4];   // the entry's pair and column, the next entry's column
+    uint32_t step[4], sf[4];             // a run's first entry: the slot's step and the filler slots before it
+    bool in[4], start[4], lead[4], half[4];
+};
+
+__device__ __forceinline__ void pair_lane(const int32_t *__restrict__ sci, int64_t z0, int64_t N, int64_t Nq, int64_t g,
+                                          int lane, PairLane &o) {
+    const int64_t i0 = (g << 8) + 4 * lane;
+    uint32_t c[6];   // the entry before, the four, the entry after
+#pragma unroll
+    for (int j = 0; j < 6; j++) c[j] = (uint32_t)sci[z0 + min(max(i0 + j - 1, (int64_t)0), N - 1)];
+    // the run holding the supergroup's first entry starts before it: found by binary search
+    const int64_t f = g << 8;
+    const uint32_t pf = (uint32_t)sci[z0 + f] >> 1;
+    int64_t gs = f;
+    if (f > 0 && ((uint32_t)sci[z0 + f - 1] >> 1) == pf) {   // uniform
+        int64_t lo = 0, hi = f;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (((uint32_t)sci[z0 + mid] >> 1) >= pf) hi = mid;
+            else lo = mid + 1;
+        }
+        gs = lo;
+    }
+    int32_t ls = -1;   // the last run start among the lane's entries (supergroup-relative)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int64_t i = i0 + j;
+        o.in[j] = i < Nq;
+        o.col[j] = c[j + 1];
+        o.next[j] = c[j + 2];
+        o.pair[j] = c[j + 1] >> 1;
+        o.start[j] = o.in[j] && (i == 0 || (c[j] >> 1) != o.pair[j]);
+        if (o.start[j]) ls = 4 * lane + j;
+    }
+    int32_t m = ls;   // inclusive max scan over the lanes
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int32_t v = __shfl_up(m, d, kWave);
+        if (lane >= d) m = max(m, v);
+    }
+    int32_t before = __shfl_up(m, 1, kWave);
+    if (lane == 0) before = -1;
+    int64_t rs = before >= 0 ? f + before : gs;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int64_t i = i0 + j;
+        if (o.start[j]) rs = i;
+        o.lead[j] = o.in[j] && (((i - rs) & 1) == 0);
+        o.half[j] = o.lead[j] && (i + 1 >= Nq || (o.next[j] >> 1) != o.pair[j]);
+        const uint32_t s0 = (o.start[j] && i > 0) ? o.pair[j] - (c[j] >> 1) : 0u;
+        o.sf[j] = s0 > 3 ? (s0 + 2) / 3 - 1 : 0u;
+        o.step[j] = s0 - 3 * o.sf[j];
+    }
+}
+
+// Slots and filler halves of every 256-entry supergroup of every sorted block.
+__global__ __launch_bounds__(256) void k_pair_cost(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
+                                                   uint32_t *__restrict__ slots, uint32_t *__restrict__ fill) {
+    const RowBlock b = blocks[blockIdx.y];
+    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, ng = (N + 255) >> 8;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < ng; g += waves) {
+        PairLane pl;
+        pair_lane(sci, z0, N, N, g, lane, pl);
+        uint32_t ns = 0, nf = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            ns += (pl.lead[j] ? 1u : 0u) + (pl.start[j] ? pl.sf[j] : 0u);
+            nf += (pl.half[j] ? 1u : 0u) + (pl.start[j] ? 2 * pl.sf[j] : 0u);
+        }
+        ns = wave_total(ns);
+        nf = wave_total(nf);
+        if (lane == 0) {
+            slots[b.seg + g] = ns;
+            fill[b.seg + g] = nf;
+        }
+    }
+}
+
+// Padding slots everywhere (step 0, both halves the lane's junk row, sel 0: in the null
+// supergroup x's zero slot) and the null supergroup's base, the pair holding x's zero slot.
+__global__ void k_pair_fill(uint32_t *__restrict__ ppk, uint64_t nslots, uint32_t *__restrict__ pbase, uint32_t null_sg,
+                            uint32_t zero_pair) {
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nslots; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t junk = (uint32_t)(kJunkRow + ((p >> 2) & (kWave - 1)));
+        ppk[p] = (junk << 15) | junk;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) pbase[null_sg] = zero_pair;
+}
+
+// The slots of the pair prefix: one wave per 256-entry supergroup g < Q of each block; lane l
+// emits the slots led by entries 4l .. 4l+3, each run's first preceded by its filler slots, at
+// the block's run + poff[g] + the lane's exclusive scan of slot counts.  Whoever emits the last
+// slot of a 256-slot supergroup stores the next one's base (the pair reached); the block's first
+// base is its first pair.  nfill: the filler halves written (statistics).
+__global__ __launch_bounds__(256) void k_pair_emit(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
+                                                   const uint32_t *__restrict__ spk, const uint32_t *__restrict__ qsplit,
+                                                   const uint32_t *__restrict__ pcount, const uint32_t *__restrict__ poff,
+                                                   const int64_t *__restrict__ pbeg, uint32_t *__restrict__ ppk,
+                                                   uint32_t *__restrict__ pbase, unsigned long long *__restrict__ nfill) {
+    const RowBlock b = blocks[blockIdx.y];
+    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, Q = qsplit[blockIdx.y];
+    const int64_t Nq = min(N, Q << 8);
+    const int64_t pb = pbeg[blockIdx.y], C = pcount[blockIdx.y];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
+    constexpr uint32_t kRowMask = (1u << kRowBits) - 1;
+    if (Q > 0 && blockIdx.x == 0 && threadIdx.x == 0) pbase[pb / kPSg] = (uint32_t)sci[z0] >> 1;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < Q; g += waves) {
+        PairLane pl;
+        pair_lane(sci, z0, N, Nq, g, lane, pl);
+        uint32_t n = 0, nf = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            n += (pl.lead[j] ? 1u : 0u) + (pl.start[j] ? pl.sf[j] : 0u);
+            nf += (pl.half[j] ? 1u : 0u) + (pl.start[j] ? 2 * pl.sf[j] : 0u);
+        }
+        int64_t pos = pb + poff[b.seg + g] + (wave_scan_incl(n) - n);   // absolute slot index
+        nf = wave_total(nf);
+        if (lane == 0 && nf) atomicAdd(nfill, (unsigned long long)nf);
+        // stored lane-major inside the 256-slot supergroup: slot e of it at (e mod 64) * 4 + e / 64
+        auto put = [&](uint32_t step, uint32_t ha, uint32_t hb, uint32_t pair_after) {
+            ppk[(pos & ~(int64_t)(kPSg - 1)) + (pos & (kWave - 1)) * 4 + ((pos >> 6) & 3)] = (step << 30) | (ha << 15) | hb;
+            const int64_t rel = pos - pb + 1;   // slots of the block up to and including this one
+            if ((rel & (kPSg - 1)) == 0 && rel < C) pbase[(pos + 1) / kPSg] = pair_after;
+            pos++;
+        };
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!pl.lead[j]) continue;
+            const int64_t e = (g << 8) + 4 * lane + j;
+            uint32_t step = 0;
+            if (pl.start[j]) {
+                uint32_t at = pl.pair[j] - pl.step[j] - 3 * pl.sf[j];
+                for (uint32_t f = 0; f < pl.sf[j]; f++) {
+                    at += 3;
+                    const uint32_t junk = (uint32_t)(kJunkRow + (pos & (kWave - 1)));   // the lane's own junk row
+                    put(3u, junk, junk, at);
+                }
+                step = pl.step[j];
+            }
+            const uint32_t ha = ((pl.col[j] & 1u) << kRowBits) | (spk[z0 + e] & kRowMask);
+            const uint32_t hb = pl.half[j] ? (uint32_t)(kJunkRow + (pos & (kWave - 1)))
+                                           : ((pl.next[j] & 1u) << kRowBits) | (spk[z0 + e + 1] & kRowMask);
+            put(step, ha, hb, pl.pair[j]);
         }
     }
 }
@@ -1451,8 +1757,23 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     const RowBlock *d_sort = p->blocks.p + longb.size();
     std::vector<uint32_t> h_nsplit(sortb.size(), 0), h_ncode(sortb.size(), 0);   // narrow prefix per sorted block
     std::vector<int64_t> h_nbeg(sortb.size(), 0);
+    std::vector<uint32_t> h_psplit(sortb.size(), 0), h_pcount(sortb.size(), 0);   // pair prefix per sorted block
+    std::vector<int64_t> h_pbeg(sortb.size(), 0);
     p->ncodes = 0;
     p->nnarrow = 0;
+    p->npair = p->npfill = p->npslots = 0;
+    // Pair slots (GX_PR_PAIRS; gather_pairs): off in a paced plan (GX_PR_PACE: its window table
+    // knows narrow and wide rounds only), which therefore keeps Q = 0 everywhere.  Every other
+    // mode (interleaved units, work queue, slab combine, GX_PR_COMBINE=1) takes the pair rounds
+    // as it takes the narrow ones.  The slots need an even chunk (a pair never straddles two
+    // ranks' chunks, and x's zero slot chunk - 2 shares its pair with the dangling slot only).
+    // On by default for a huge graph's single plan only, where it was measured to win (SYN-8_5,
+    // alternated runs: 605.8-608.7 us per launch against 626.8-629.2 without); SYN-7_5 ran
+    // 76.0-78.8 us against 72.9-73.7, and a block partition's pieces were not measured
+    // (DESIGN.md 4).
+    const bool pairs_on =
+        env_int("GX_PR_PAIRS", huge && !piece ? 1 : 0, 0, 1) == 1 && env_int("GX_PR_PACE", 0, 0, 1) == 0;
+    if (pairs_on && (p->chunk & 1)) return fail(GX_INVALID_VALUE, "pr_plan_sorted: pair slots need an even chunk");
     // device temporaries of the plan, released after the unit-size search (which runs on the
     // host while the narrow codes and the lane permutation are built)
     DBuf<int32_t> d_seg_row;
@@ -1462,6 +1783,9 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     DBuf<PackChunk> d_pch;
     DBuf<uint32_t> d_fill, d_noff, d_nsplit, d_ncode;
     DBuf<int64_t> d_nbeg;
+    DBuf<uint32_t> d_pslots, d_pfill, d_poff, d_psplit, d_pcount;
+    DBuf<int64_t> d_pbeg;
+    DBuf<unsigned long long> d_npfill;
     if (nnz > 0) {
         // segments in row order: the sorted blocks and the LONG rows
         std::vector<std::pair<int32_t, int32_t>> order_;   // (first row, index: block i >= 0, LONG row -1 - j)
@@ -1583,20 +1907,66 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             GX_TRY(d_nsplit.alloc(nsb));
             GX_TRY(d_ncode.alloc(nsb));
             GX_TRY(d_nbeg.alloc(nsb));
-            hipLaunchKernelGGL(k_narrow_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_fill.p);
+            // the pair prefixes Q first: the prefix of supergroups maximising entries - w fillers
+            // (w = GX_PR_PAIR_FILL_COST / 4 entries per filler half; SYN-8_5, us per launch:
+            // w = 1 613-616, 3 613-617, 6 610-611, 12 606-609), in blocks of at least
+            // GX_PR_PAIR_MIN entries; the narrow codes then start at Q
+            GX_TRY(d_psplit.alloc(nsb));
+            GX_TRY(d_pcount.alloc(nsb));
+            GX_TRY(d_pbeg.alloc(nsb));
+            GX_TRY(d_npfill.alloc(1));
+            GX_HIP_TRY(hipMemsetAsync(d_psplit.p, 0, nsb * 4, s));
+            GX_HIP_TRY(hipMemsetAsync(d_npfill.p, 0, sizeof(unsigned long long), s));
+            if (pairs_on) {
+                GX_TRY(d_pslots.alloc(std::max<int64_t>(ngroups, 1)));
+                GX_TRY(d_pfill.alloc(std::max<int64_t>(ngroups, 1)));
+                GX_TRY(d_poff.alloc(std::max<int64_t>(ngroups, 1)));
+                hipLaunchKernelGGL(k_pair_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_pslots.p, d_pfill.p);
+                GX_TRY(check_launch("k_pair_cost"));
+                hipLaunchKernelGGL(k_narrow_split, dim3(nsb), dim3(1024), 0, s, d_sort, d_pfill.p, d_pslots.p,
+                                   env_int("GX_PR_PAIR_FILL_COST", 48, 0, 1 << 20), (const uint32_t *)nullptr, 1,
+                                   (int64_t)env_int("GX_PR_PAIR_MIN", 0, 0, 1 << 30), d_psplit.p, d_pcount.p, d_poff.p);
+                GX_TRY(check_launch("k_narrow_split (pairs)"));
+                GX_HIP_TRY(hipMemcpyAsync(h_psplit.data(), d_psplit.p, nsb * 4, hipMemcpyDeviceToHost, s));
+                GX_HIP_TRY(hipMemcpyAsync(h_pcount.data(), d_pcount.p, nsb * 4, hipMemcpyDeviceToHost, s));
+            }
+            hipLaunchKernelGGL(k_narrow_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_psplit.p, d_fill.p);
             GX_TRY(check_launch("k_narrow_cost"));
-            hipLaunchKernelGGL(k_narrow_split, dim3(nsb), dim3(1024), 0, s, d_sort, d_fill.p,
-                               env_int("GX_PR_NARROW", 1, 0, 1), (int64_t)env_int("GX_PR_NARROW_MIN", 0, 0, 1 << 30),
-                               d_nsplit.p, d_ncode.p, d_noff.p);
+            hipLaunchKernelGGL(k_narrow_split, dim3(nsb), dim3(1024), 0, s, d_sort, d_fill.p, (const uint32_t *)nullptr, 4,
+                               d_psplit.p, env_int("GX_PR_NARROW", 1, 0, 1),
+                               (int64_t)env_int("GX_PR_NARROW_MIN", 0, 0, 1 << 30), d_nsplit.p, d_ncode.p, d_noff.p);
             GX_TRY(check_launch("k_narrow_split"));
             GX_HIP_TRY(hipMemcpyAsync(h_nsplit.data(), d_nsplit.p, nsb * 4, hipMemcpyDeviceToHost, s));
             GX_HIP_TRY(hipMemcpyAsync(h_ncode.data(), d_ncode.p, nsb * 4, hipMemcpyDeviceToHost, s));
             GX_HIP_TRY(hipStreamSynchronize(s));
-            uint64_t run = 0;
+            uint64_t run = 0, prun = 0;
             for (size_t i = 0; i < sortb.size(); i++) {
+                const int64_t E = sortb[i].nz_end - sortb[i].nz_begin;
+                const int64_t Ep = std::min<int64_t>((int64_t)h_psplit[i] * 256, E);
                 h_nbeg[i] = (int64_t)run;
                 run += ((uint64_t)h_ncode[i] + kNSg - 1) / kNSg * kNSg;
-                p->nnarrow += (uint64_t)std::min<int64_t>((int64_t)h_nsplit[i] * 256, sortb[i].nz_end - sortb[i].nz_begin);
+                p->nnarrow += (uint64_t)(std::min<int64_t>((int64_t)h_nsplit[i] * 256, E) - Ep);
+                h_pbeg[i] = (int64_t)prun;
+                prun += ((uint64_t)h_pcount[i] + kPSg - 1) / kPSg * kPSg;
+                p->npair += (uint64_t)Ep;
+            }
+            // the pair slots: padding everywhere, then each block's prefix
+            p->pnull_sg = (uint32_t)(prun / kPSg);
+            p->npslots = prun + kPSg;
+            GX_TRY(p->ppk.alloc(p->npslots, 16));
+            GX_TRY(p->pbase.alloc(p->npslots / kPSg));
+            hipLaunchKernelGGL(k_pair_fill, dim3(grid_for(p->npslots, 256, 16384)), dim3(256), 0, s, p->ppk.p, p->npslots,
+                               p->pbase.p, p->pnull_sg, (uint32_t)((p->chunk - 2) >> 1));
+            GX_TRY(check_launch("k_pair_fill"));
+            if (p->npair) {
+                GX_HIP_TRY(hipMemcpyAsync(d_pbeg.p, h_pbeg.data(), nsb * 8, hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL(k_pair_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_psplit.p,
+                                   d_pcount.p, d_poff.p, d_pbeg.p, p->ppk.p, p->pbase.p, d_npfill.p);
+                GX_TRY(check_launch("k_pair_emit"));
+                unsigned long long nf = 0;
+                GX_HIP_TRY(hipMemcpyAsync(&nf, d_npfill.p, sizeof nf, hipMemcpyDeviceToHost, s));
+                GX_HIP_TRY(hipStreamSynchronize(s));
+                p->npfill = nf;
             }
             p->null_sg = (uint32_t)(run / kNSg);
             p->ncodes = run + kNSg;
@@ -1606,7 +1976,7 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             hipLaunchKernelGGL(k_narrow_fill, dim3(grid_for(p->ncodes, 256, 16384)), dim3(256), 0, s, p->npk.p, p->ncodes,
                                p->nbase.p, p->null_sg, (uint32_t)(p->chunk - 2));
             GX_TRY(check_launch("k_narrow_fill"));
-            hipLaunchKernelGGL(k_narrow_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_nsplit.p,
+            hipLaunchKernelGGL(k_narrow_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_psplit.p, d_nsplit.p,
                                d_ncode.p, d_noff.p, d_nbeg.p, p->npk.p, p->nbase.p);
             GX_TRY(check_launch("k_narrow_emit"));
             clk.mark("narrow codes");
@@ -1642,11 +2012,17 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     // priced as entries ran faster than at the fitted 2x (139 against 150 us per piece launch)
     const bool cost_codes = env_int("GX_PR_COST_CODES", piece ? 1 : 0, 0, 1) == 1;
     const int64_t fill_cost4 = env_int("GX_PR_FILL_COST", 4, 0, 64);
+    // GX_PR_PAIR_COST: an entry held in a pair slot, in quarters of a narrow entry's cost (its
+    // filler halves, where the codes are priced, at the same rate)
+    const int64_t pair_cost4 = env_int("GX_PR_PAIR_COST", 4, 1, 64);
     auto eff_entries = [&](int64_t i) -> int64_t {
         const int64_t E = sortb[i].nz_end - sortb[i].nz_begin;
-        const int64_t En = std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]);
+        const int64_t Ep = std::min<int64_t>(E, 256 * (int64_t)h_psplit[i]);       // in pair slots
+        const int64_t Enp = std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]);      // pair slots + narrow codes
+        const int64_t En = Enp - Ep;
         const int64_t fill = cost_codes ? std::max<int64_t>(0, (int64_t)h_ncode[i] - En) : 0;
-        return En + fill * fill_cost4 / 4 + (E - En) * wide_cost4 / 4;
+        const int64_t pent = cost_codes ? std::max<int64_t>(Ep, 2 * (int64_t)h_pcount[i]) : Ep;
+        return pent * pair_cost4 / 4 + En + fill * fill_cost4 / 4 + (E - Enp) * wide_cost4 / 4;
     };
     // huge graphs: units per block by weighted entries (GX_PR_UNIT_BY_COST=0: by entries), so a
     // block of mostly wide entries, ~half the hub blocks' entry rate, is cut into more units
@@ -1754,6 +2130,9 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
                 u.slab = k > 1 ? slab : 0;
                 u.nbeg = h_nbeg[i];
                 u.nsg = (int32_t)(((int64_t)h_ncode[i] + kNSg - 1) / kNSg);
+                u.pbeg = h_pbeg[i];
+                u.psg = (int32_t)(((int64_t)h_pcount[i] + kPSg - 1) / kPSg);
+                u.pad = 0;
                 u.seg = b.seg;
                 u.z0 = b.nz_begin;
                 u.z1 = b.nz_end;
@@ -1767,7 +2146,7 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             }
             if (env_int("GX_PR_VERBOSE", 0, 0, 3) == 3)
                 std::fprintf(stderr, "[gx_pr blk] %zu E %lld En %lld codes %u eff %lld k %d rows %lld\n", i, (long long)E,
-                             (long long)std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]), h_ncode[i],
+                             (long long)(std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]) - std::min<int64_t>(E, 256 * (int64_t)h_psplit[i])), h_ncode[i],
                              (long long)eff_entries((int64_t)i), k, (long long)rows_b);
             if (k > 1) {
                 if (p->comb_kernel)
@@ -1806,6 +2185,18 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
                          (long long)rows, (unsigned long long)nnz, (long long)T,
                          p->sorted_nnz, p->long_nnz, sortb.size(), p->nlong_blocks, p->nlong, p->nunits, parts,
                          (long long)slab, (unsigned long long)p->nnarrow, (unsigned long long)p->ncodes);
+        if (env_int("GX_PR_VERBOSE", 0, 0, 3) && pairs_on) {
+            size_t nq = 0;
+            uint64_t qsum = 0;
+            for (uint32_t q : h_psplit) {
+                nq += q > 0;
+                qsum += q;
+            }
+            std::fprintf(stderr, "[gx_pr] pairs: %llu entries and %llu filler halves in %llu slots (padding included); "
+                         "%zu of %zu blocks with a pair prefix, mean Q %.1f supergroups\n",
+                         (unsigned long long)p->npair, (unsigned long long)p->npfill, (unsigned long long)p->npslots, nq,
+                         h_psplit.size(), nq ? (double)qsum / (double)nq : 0.0);
+        }
         GX_TRY(p->units.alloc(units.size()));
         GX_HIP_TRY(hipMemcpy(p->units.p, units.data(), units.size() * sizeof(SortedUnit), hipMemcpyHostToDevice));
         GX_TRY(p->uslab.alloc(std::max<int64_t>(slab, 1)));
@@ -1921,6 +2312,12 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
     a.nbase = p->nbase.p;
     a.null_sg = p->null_sg;
     a.nt_col = p->nt_col;
+    a.ppk = p->ppk.p;
+    a.pbase = p->pbase.p;
+    a.pnull_sg = p->pnull_sg;
+    // a pair slot's one load reads x[2p] and x[2p + 1]
+    if (p->npair && (reinterpret_cast<uintptr_t>(x_full) & 15))
+        return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots need x 16-byte aligned");
     a.pace_rounds = p->pace_rounds.p;
     a.pace_prog = p->pace_prog.p;
     a.pace_nw = p->pace_nw;
@@ -1956,7 +2353,7 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
                                  else hipLaunchKernelGGL((k_pr_pull_units<false, k>), dim3(nw), dim3(kBS), lds, s, a); break;
                 GX_PROBE_CASE(1) GX_PROBE_CASE(2) GX_PROBE_CASE(3) GX_PROBE_CASE(4) GX_PROBE_CASE(5) GX_PROBE_CASE(6) GX_PROBE_CASE(7)
                 GX_PROBE_CASE(8) GX_PROBE_CASE(9) GX_PROBE_CASE(10) GX_PROBE_CASE(11) GX_PROBE_CASE(12)
-                GX_PROBE_CASE(13) GX_PROBE_CASE(14) GX_PROBE_CASE(15) GX_PROBE_CASE(16) GX_PROBE_CASE(17) GX_PROBE_CASE(18)
+                GX_PROBE_CASE(13) GX_PROBE_CASE(14) GX_PROBE_CASE(15) GX_PROBE_CASE(16) GX_PROBE_CASE(17) GX_PROBE_CASE(18) GX_PROBE_CASE(19)
 #undef GX_PROBE_CASE
                 default: hipLaunchKernelGGL((k_pr_pull_units<false>), dim3(nw), dim3(kBS), lds, s, a);
                 }
@@ -2007,6 +2404,8 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
                         for (int64_t k0 = u.lo; k0 < u.hi; k0 += u.step) ents += std::min<int64_t>(u.step / u.nunits, u.hi - k0);
                         for (int64_t r = u.unit; r * 16 < u.nsg; r += u.nunits)   // narrow codes (fillers included)
                             ents += std::min<int64_t>(16, u.nsg - r * 16) * kNSg;
+                        for (int64_t r = u.unit; r * 16 < u.psg; r += u.nunits)   // pair slots, two entries each
+                            ents += std::min<int64_t>(16, u.psg - r * 16) * kPSg * 2;
                         blk = u.blk;
                         unit = u.unit;
                         nunits = u.nunits;
