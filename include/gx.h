@@ -119,6 +119,14 @@ int gx_graph_info(gx_graph *g, uint64_t *n, uint64_t *nnz, int *directed, int *w
 /* LAGr_BreadthFirstSearch(&level, NULL, G, src) (bfs.cpp:80).  level[v] = hop count
  * over out-edges, INT64_MAX when unreachable (bfs.cpp:53-61). */
 int gx_bfs(gx_graph *g, uint64_t src, int64_t *level);
+/* LAGr_BreadthFirstSearch(&level, &parent, G, src), both outputs.  level as gx_bfs (may be NULL).
+ * parent[src] = src; parent[v] = -1 when v is unreachable; otherwise the SMALLEST internal index u
+ * (A's vertex order) with A(u,v) stored and level[u] == level[v] - 1.  LAGraph's `any` monoid may
+ * return any such u; taking the smallest makes the tree unique, so it is bit-exact whichever way
+ * the traversal went, the same on the hub-first copy a repeated call runs on, and the same as the
+ * GX_MIN_SECONDI_INT64 loop below.  The levels come from gx_bfs's traversal; one more pass over
+ * the edges derives the parents from them.  Counts as a BFS call on g (transpose, copy). */
+int gx_bfs_parent(gx_graph *g, uint64_t src, int64_t *level, int64_t *parent);
 
 /* LAGr_PageRankGX(&r, &iters, G, damping, itermax) incl. LAGraph_Cached_OutDegree /
  * LAGraph_Cached_AT (pr.cpp:58-61).  Graphalytics PR with dangling redistribution,
@@ -166,14 +174,20 @@ int gx_lcc(gx_graph *g, double *lcc);
  *   GX_ANY_PAIR_BOOL      (presence) / uint8   BFS frontier vxm (bfs.cpp:80)
  *   GX_MIN_PLUS_FP64      double / double      SSSP relaxation vxm (sssp.cpp:78)
  *   GX_PLUS_PAIR_INT64    (presence) / int64   triangle counts (lcc.cpp:68)
+ *   GX_MIN_SECONDI_INT64  (presence) / int64   the parent BFS's vxm q<!pi, replace> = q any.secondi A
+ *                                              (LAGr_BreadthFirstSearch with a parent), `any`
+ *                                              resolved to `min`: mult yields the contracted index
+ *                                              (i in t(j) = min_i {i : u(i) present, A(i,j)} for
+ *                                              vxm, j for mxv); identity INT64_MAX
  * gx_mxv: t(i) = (+)_j mult(M(i,j), u(j)) over stored M(i,j) and present u(j), M = A (A' with
  *         GX_DESC_T0);  gx_vxm: t(j) = (+)_i mult(u(i), A(i,j)) (A' with GX_DESC_T0);
- *         SECOND(x,y) = y, PLUS(x,y) = x+y, PAIR = 1; t(i) present iff a term exists.  Then
+ *         SECOND(x,y) = y, PLUS(x,y) = x+y, PAIR = 1, SECONDI = the index the two operands
+ *         share; t(i) present iff a term exists.  Then
  *         w<mask> = t, or w (+)= t with GX_DESC_ACCUM (old w present per w_present, or all
  *         when it is NULL); mask = n structural bytes or NULL, complemented by
  *         GX_DESC_MASK_COMP; masked-out entries are kept, or cleared by GX_DESC_REPLACE.
  *         w is read (for the kept / accumulated entries) and written; w_present, if given,
- *         likewise.  u may be NULL for the PAIR semirings and vxm's SECOND ones.
+ *         likewise.  u may be NULL for the PAIR and SECONDI semirings and vxm's SECOND ones.
  * gx_mxm_masked: C<A> = A (+).(x) A' with GX_PLUS_PAIR_INT64 and desc 0: c[e] for the stored
  *         entry e = (i, j) of A (in A's entry order, nnz values) is |{k : A(i,k), A(j,k)}|,
  *         the dot product of rows i and j (rows must not repeat a column).  Other semirings
@@ -184,6 +198,7 @@ int gx_lcc(gx_graph *g, double *lcc);
 #define GX_ANY_PAIR_BOOL 2
 #define GX_MIN_PLUS_FP64 3
 #define GX_PLUS_PAIR_INT64 4
+#define GX_MIN_SECONDI_INT64 5
 #define GX_DESC_T0 1          /* GrB_INP0 = GrB_TRAN */
 #define GX_DESC_MASK_COMP 2   /* GrB_MASK = GrB_COMP (structural mask) */
 #define GX_DESC_REPLACE 4     /* GrB_OUTP = GrB_REPLACE */

@@ -103,6 +103,17 @@ def LA_BFS(G: Graph, source_vertex: int) -> np.ndarray:
     return out
 
 
+def LA_BFS_parent(G: Graph, source_vertex: int):
+    """LAGr_BreadthFirstSearch with both outputs (gx_bfs_parent): (level, parent), int64 each.
+    level as LA_BFS; parent[source] = source, -1 for unreachable vertices, else the smallest
+    vertex one level up with an edge to the vertex."""
+    level = np.empty(G.n, dtype=np.int64)
+    parent = np.empty(G.n, dtype=np.int64)
+    N.check(N.lib().gx_bfs_parent(G.handle, int(source_vertex), N.as_i64p(level), N.as_i64p(parent)),
+            "gx_bfs_parent")
+    return level, parent
+
+
 def LA_PR(G: Graph, damping_factor: float, iteration_num: int) -> np.ndarray:
     """pr.cpp:47-66: Graphalytics PageRank, fp64."""
     out = np.empty(G.n, dtype=np.float64)
@@ -177,9 +188,10 @@ def LA_LCC(G: Graph) -> np.ndarray:
 
 # ---- op-level GraphBLAS calls (include/gx.h gx_mxv / gx_vxm / gx_mxm_masked) ----
 PLUS_SECOND_FP64, MIN_SECOND_UINT64, ANY_PAIR_BOOL, MIN_PLUS_FP64, PLUS_PAIR_INT64 = range(5)
+MIN_SECONDI_INT64 = 5
 DESC_T0, DESC_MASK_COMP, DESC_REPLACE, DESC_ACCUM = 1, 2, 4, 8
 _OUT_DTYPE = {PLUS_SECOND_FP64: np.float64, MIN_SECOND_UINT64: np.uint64, ANY_PAIR_BOOL: np.uint8,
-              MIN_PLUS_FP64: np.float64, PLUS_PAIR_INT64: np.int64}
+              MIN_PLUS_FP64: np.float64, PLUS_PAIR_INT64: np.int64, MIN_SECONDI_INT64: np.int64}
 
 
 def _vp(a):

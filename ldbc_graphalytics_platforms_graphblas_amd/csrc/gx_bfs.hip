@@ -11,6 +11,8 @@
 //               neighbours at a time, until it meets a frontier vertex.
 // Direction switching follows Beamer's heuristic (alpha = 14, beta = 24).  Levels are
 // unique, so the result is bit-exact whatever the traversal order.
+// gx_bfs_parent (LAGr_BreadthFirstSearch with its parent output) runs the same levels, then one
+// pass over the edges that gives every reached vertex its smallest parent (below, "parents").
 #include <cstdlib>
 #include <memory>
 
@@ -420,19 +422,158 @@ __global__ void k_bfs_seed(const int64_t *__restrict__ rp, int32_t *level, uint6
     if (threadIdx.x == 0) *qcount = nch;
 }
 
-}  // namespace
-}  // namespace gx
+// ---- parents from the finished levels (gx_bfs_parent) ------------------------------------
+// parent[v] = the smallest candidate u with A(u,v) stored and level[u] == level[v] - 1, where
+// the candidate of u is its id in the caller's vertex order (order[u] on a hub-first copy, so
+// the minimum is the same on the copy as on the graph itself).  The level kernels cannot give
+// it: the top-down claim is first-come and the bottom-up scan stops at its first hit.
+//   pull : (in-edges resident, as for bottom-up) every reached v scans its whole in-row -- rows
+//          are not sorted in the candidates' id space, so the first hit is not the minimum.  A
+//          row of at most kParentShort entries is one thread's work; a longer one becomes
+//          (vertex, chunk) items of kChunk entries, one wave each, like the top-down frontier:
+//          the wave reduces its minimum and stores it (one chunk) or atomicMin's it (several).
+//   push : (a directed graph without its transpose) every reached u walks its out-row, same
+//          split, and offers its candidate to each v one level down with atomicMin, behind a
+//          plain read of parent[v]: candidates only fall, so a stale read costs one atomic at
+//          most, and most offers lose to an earlier smaller one without leaving the CU.
+// Unreached vertices read -1; in push the identity INT32_MAX stands until k_bfs_parent_fin.
+constexpr int kParentShort = 64;   // GX_BFS_PARENT_SHORT overrides (16-256 within 7 % on a copy)
+constexpr int32_t kNoParent = INT32_MAX;
 
-using namespace gx;
+__device__ __forceinline__ int32_t parent_cand(const int32_t *__restrict__ order, int32_t u) {
+    return order ? order[u] : u;
+}
 
-extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
-    if (!g || !level_out) return fail(GX_NULL_POINTER, "gx_bfs: null argument");
-    if (src >= g->n) return fail(GX_INVALID_INDEX, "gx_bfs: source out of range");
-    {
-        gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
-        GX_TRY(hub_for(g, ++g->hub_bfs_calls, &h, &src));
-        if (h) return gx_bfs(h, src, level_out);
+// pull: is u a parent of a vertex whose level is lv1 + 1?  push: is v a child of one at lv1 - 1?
+template <bool PUSH>
+__device__ __forceinline__ void parent_edge(const int32_t *__restrict__ level,
+                                            const int32_t *__restrict__ order, int32_t x, int32_t lv1,
+                                            int32_t mine, int32_t *parent, int32_t &m) {
+    if (level[x] != lv1) return;
+    if constexpr (PUSH) {
+        if (parent[x] > mine) atomicMin(&parent[x], mine);
+    } else {
+        m = min(m, parent_cand(order, x));
     }
+}
+
+// One thread per vertex: the short rows whole, the long ones queued as items for
+// k_bfs_parent_long (a wave covers 64 consecutive vertices per round: wave_append shuffles).
+template <bool PUSH>
+__global__ __launch_bounds__(kBfsBlock) void k_bfs_parent_rows(const int64_t *__restrict__ rp,
+                                                               const int32_t *__restrict__ ci,
+                                                               const int32_t *__restrict__ level,
+                                                               const int32_t *__restrict__ order, int64_t n,
+                                                               int32_t *parent, uint64_t *items,
+                                                               uint32_t *nitems, int short_deg) {
+    const int64_t stride = (int64_t)gridDim.x * kBfsBlock;
+    const int64_t nround = (n + stride - 1) / stride;
+    for (int64_t r = 0; r < nround; r++) {
+        const int64_t v = r * stride + (int64_t)blockIdx.x * kBfsBlock + threadIdx.x;
+        uint32_t nch = 0;
+        if (v < n) {
+            const int32_t lv = level[v];
+            if (!PUSH && lv <= 0) {
+                parent[v] = lv < 0 ? -1 : parent_cand(order, (int32_t)v);   // unreached; the source
+            } else if (lv >= 0) {
+                const int64_t b = rp[v], e = rp[v + 1];
+                if (e - b > short_deg) {
+                    nch = chunks_of(e - b);
+                    if (!PUSH) parent[v] = kNoParent;
+                } else {
+                    const int32_t lv1 = PUSH ? lv + 1 : lv - 1;
+                    const int32_t mine = PUSH ? parent_cand(order, (int32_t)v) : 0;
+                    int32_t m = kNoParent;
+                    for (int64_t k = b; k < e; k += 4) {   // four independent level probes in flight
+                        const int32_t x0 = ci[k];
+                        const int32_t x1 = ci[min(k + 1, e - 1)];
+                        const int32_t x2 = ci[min(k + 2, e - 1)];
+                        const int32_t x3 = ci[min(k + 3, e - 1)];
+                        parent_edge<PUSH>(level, order, x0, lv1, mine, parent, m);
+                        parent_edge<PUSH>(level, order, x1, lv1, mine, parent, m);
+                        parent_edge<PUSH>(level, order, x2, lv1, mine, parent, m);
+                        parent_edge<PUSH>(level, order, x3, lv1, mine, parent, m);
+                    }
+                    if (!PUSH) parent[v] = m;
+                }
+            }
+        }
+        wave_append(nch != 0, (int32_t)v, nch, items, nitems);
+    }
+}
+
+// One wave per (vertex, chunk) item of a long row.
+template <bool PUSH>
+__global__ __launch_bounds__(kBfsBlock) void k_bfs_parent_long(const int64_t *__restrict__ rp,
+                                                               const int32_t *__restrict__ ci,
+                                                               const int32_t *__restrict__ level,
+                                                               const int32_t *__restrict__ order,
+                                                               const uint64_t *__restrict__ items,
+                                                               const uint32_t *__restrict__ nitems,
+                                                               int32_t *parent) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = (blockIdx.x * kBfsBlock + threadIdx.x) / kWave;
+    const uint32_t nwaves = gridDim.x * (kBfsBlock / kWave);
+    const uint32_t count = *nitems;
+    for (uint32_t f = wave; f < count; f += nwaves) {
+        const uint64_t item = items[f];
+        const int32_t v = (int32_t)(item >> 32);
+        const int64_t b0 = rp[v], e = rp[v + 1];
+        const int64_t b = b0 + (int64_t)(uint32_t)item * kChunk;
+        const int64_t end = min(e, b + kChunk);
+        const int32_t lv1 = PUSH ? level[v] + 1 : level[v] - 1;
+        const int32_t mine = PUSH ? parent_cand(order, v) : 0;
+        int32_t m = kNoParent;
+#pragma unroll
+        for (int i = 0; i < kChunk / kWave; i++) {
+            const int64_t k = b + lane + (int64_t)i * kWave;
+            if (k < end) parent_edge<PUSH>(level, order, ci[k], lv1, mine, parent, m);
+        }
+        if constexpr (!PUSH) {
+            for (int off = 32; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off, kWave));
+            if (lane == 0) {
+                if (e - b0 <= kChunk) parent[v] = m;   // the row's only chunk
+                else if (m != kNoParent) atomicMin(&parent[v], m);
+            }
+        }
+    }
+}
+
+// push: the atomicMin identity everywhere but at the source, and back to -1 where it stood
+__global__ __launch_bounds__(kBfsBlock) void k_bfs_parent_init(const int32_t *__restrict__ level,
+                                                               const int32_t *__restrict__ order, int64_t n,
+                                                               int32_t *__restrict__ parent) {
+    for (int64_t v = (int64_t)blockIdx.x * kBfsBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBfsBlock)
+        parent[v] = level[v] == 0 ? parent_cand(order, (int32_t)v) : kNoParent;
+}
+
+__global__ __launch_bounds__(kBfsBlock) void k_bfs_parent_fin(int64_t n, int32_t *__restrict__ parent) {
+    for (int64_t v = (int64_t)blockIdx.x * kBfsBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBfsBlock)
+        if (parent[v] == kNoParent) parent[v] = -1;
+}
+
+// The buffers of one BFS: owned by the entry point, so they are released after its download.
+struct BfsWork {
+    DBuf<int32_t> level;   // the result, in g's vertex order: -1 = unreached
+    DBuf<uint64_t> q0, q1;
+    DBuf<uint32_t> qcount;
+    DBuf<unsigned long long> nedges;
+    DBuf<uint64_t> fbits;
+    DBuf<unsigned long long> bucnt;
+    DBuf<BfsState> st;
+    std::unique_ptr<int32_t, void (*)(int32_t *)> done_guard{nullptr, [](int32_t *p) { (void)hipHostFree(p); }};
+    std::unique_ptr<ihipEvent_t, void (*)(hipEvent_t)> ev_guard{nullptr, [](hipEvent_t e) { (void)hipEventDestroy(e); }};
+    const DevCSR *in = nullptr;   // the in-edges the bottom-up levels read (nullptr: none resident)
+};
+
+// The levels of a BFS of g (not a graph with a hub-first copy to run on: the entry points go
+// through hub_for first) from src, left on the device in w.level; device_begin is called, the
+// caller ends the bracket.  tail(early) queues the caller's work behind the last level (the
+// results' remap, the parent pass) and returns whether it did: with early set it is queued
+// behind the levels expected to be the last, before the host knows they are, and is asked for
+// again if they were not.
+template <typename Tail>
+int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail) {
     gx_ctx *ctx = g->ctx;
     GX_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -440,12 +581,12 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
     int64_t src_rp[2] = {0, 0};   // the source's out-degree (the host row pointers are lazy)
     GX_HIP_TRY(hipMemcpy(src_rp, g->A.rp.p + src, sizeof(src_rp), hipMemcpyDeviceToHost));
     const int64_t src_deg = src_rp[1] - src_rp[0];
-    DBuf<int32_t> level;
-    DBuf<uint64_t> q0, q1;
-    DBuf<uint32_t> qcount;
-    DBuf<unsigned long long> nedges;
-    DBuf<uint64_t> fbits;
-    DBuf<unsigned long long> bucnt;
+    DBuf<int32_t> &level = w.level;
+    DBuf<uint64_t> &q0 = w.q0, &q1 = w.q1;
+    DBuf<uint32_t> &qcount = w.qcount;
+    DBuf<unsigned long long> &nedges = w.nedges;
+    DBuf<uint64_t> &fbits = w.fbits;
+    DBuf<unsigned long long> &bucnt = w.bucnt;
     GX_TRY(fbits.alloc(2 * ((n + 63) / 64)));   // two bitmaps: the device-driven path alternates them
     uint64_t *const fb1 = fbits.p + (n + 63) / 64;
     GX_TRY(bucnt.alloc(2));
@@ -467,13 +608,14 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
         if (mode == 2 || (mode == 1 && g->bfs_calls >= 2)) GX_TRY(ensure_transpose(g));
     }
     const DevCSR *in = g->directed ? (g->AT.built ? &g->AT : nullptr) : &g->A;
+    w.in = in;
     GX_HIP_TRY(hipMemsetAsync(level.p, 0xff, n * 4, s));
     const unsigned bu_grid = (unsigned)std::min<int64_t>(grid_for(n, kBfsBlock, 8192), 1024);
     const char *de = std::getenv("GX_BFS_DEVICE");
     if (!de || std::atoi(de) != 0) {
         // device-driven levels (k_bfs_plan), queued in batches; the done flag is read one
         // batch late
-        DBuf<BfsState> st;
+        DBuf<BfsState> &st = w.st;
         GX_TRY(st.alloc(1));
         BfsState h{};
         const int64_t dsrc = src_deg;
@@ -499,9 +641,9 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
         int32_t *h_done = nullptr;
         hipEvent_t ev = nullptr;
         GX_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_done), 4 * sizeof(int32_t), hipHostMallocDefault));
-        std::unique_ptr<int32_t, void (*)(int32_t *)> done_guard(h_done, [](int32_t *p) { (void)hipHostFree(p); });
+        w.done_guard.reset(h_done);
         GX_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        std::unique_ptr<ihipEvent_t, void (*)(hipEvent_t)> ev_guard(ev, [](hipEvent_t e) { (void)hipEventDestroy(e); });
+        w.ev_guard.reset(ev);
         // grids of the kernels that run idle on the levels of the other direction: an idle
         // 8192-workgroup launch cost 2.6-3.0 us, a 2048 one 0.9 (r04_bfs_kernel_stats.csv);
         // every kernel is a grid-stride loop (GX_BFS_GRID overrides)
@@ -558,14 +700,14 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
             GX_HIP_TRY(hipEventRecord(ev, s));
             return GX_SUCCESS;
         };
-        const void *res = nullptr;
+        bool queued = false;
         GX_TRY(enqueue(first));
         int64_t levels = first;
         GX_TRY(read_state());
         if (g->bfs_steps_hint > 0) {
-            // the results' remap is queued behind the levels it expects to be the last, so it
-            // runs while the host reads the flag (queued again below if they were not)
-            GX_TRY(remap_out(g, level.p, 4, s, &res));
+            // the tail (the results' remap) is queued behind the levels it expects to be the
+            // last, so it runs while the host reads the flag (queued again below if they were not)
+            GX_TRY(tail(true, queued));
             GX_HIP_TRY(hipEventSynchronize(ev));
         } else {
             GX_TRY(enqueue(kBatch));
@@ -582,9 +724,7 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
         }
         // steps this BFS needed: its levels plus the plan step that found the frontier empty
         g->bfs_steps_hint = h_done[0] + 1;
-        if (!res || more) GX_TRY(remap_out(g, level.p, 4, s, &res));
-        GX_TRY(device_end(ctx));
-        GX_TRY(download(ctx, level_out, res, (uint64_t)n, Xfer::Levels));
+        if (!queued || more) GX_TRY(tail(false, queued));
         return GX_SUCCESS;
     }
     hipLaunchKernelGGL(k_bfs_seed, dim3(1), dim3(256), 0, s, g->A.rp.p, level.p, q0.p, qcount.p, (int32_t)src);
@@ -659,10 +799,87 @@ extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
         fsize = next_size;
         depth++;
     }
+    bool queued = false;
+    return tail(false, queued);
+}
+
+// The parent pass over w's finished levels into parent (n words, g's vertex order, candidates
+// in the caller's ids); the items of the long rows reuse the level loop's queue.
+int bfs_parents(gx_graph *g, BfsWork &w, int32_t *parent, hipStream_t s) {
+    const int64_t n = (int64_t)g->n;
+    const unsigned vgrid = grid_for(n, kBfsBlock, 8192), lgrid = 2048;
+    const char *se = std::getenv("GX_BFS_PARENT_SHORT");   // rows up to this length are one thread's
+    const int short_deg = se ? std::max(0, std::atoi(se)) : kParentShort;
+    KTimer kt(g->ctx, "bfs_parents", s);
+    GX_HIP_TRY(hipMemsetAsync(w.qcount.p, 0, 4, s));
+    // pull wherever gx_bfs would go bottom-up; GX_BFS_PARENT_PUSH=1 takes push there too (A/B)
+    const char *pe = std::getenv("GX_BFS_PARENT_PUSH");
+    if (w.in && !(pe && std::atoi(pe) != 0)) {
+        hipLaunchKernelGGL(k_bfs_parent_rows<false>, dim3(vgrid), dim3(kBfsBlock), 0, s, w.in->rp.p, w.in->ci.p,
+                           w.level.p, g->out_order, n, parent, w.q0.p, w.qcount.p, short_deg);
+        hipLaunchKernelGGL(k_bfs_parent_long<false>, dim3(lgrid), dim3(kBfsBlock), 0, s, w.in->rp.p, w.in->ci.p,
+                           w.level.p, g->out_order, w.q0.p, w.qcount.p, parent);
+        return check_launch("k_bfs_parent_long");
+    }
+    hipLaunchKernelGGL(k_bfs_parent_init, dim3(vgrid), dim3(kBfsBlock), 0, s, w.level.p, g->out_order, n, parent);
+    hipLaunchKernelGGL(k_bfs_parent_rows<true>, dim3(vgrid), dim3(kBfsBlock), 0, s, g->A.rp.p, g->A.ci.p, w.level.p,
+                       g->out_order, n, parent, w.q0.p, w.qcount.p, short_deg);
+    hipLaunchKernelGGL(k_bfs_parent_long<true>, dim3(lgrid), dim3(kBfsBlock), 0, s, g->A.rp.p, g->A.ci.p, w.level.p,
+                       g->out_order, w.q0.p, w.qcount.p, parent);
+    hipLaunchKernelGGL(k_bfs_parent_fin, dim3(vgrid), dim3(kBfsBlock), 0, s, n, parent);
+    return check_launch("k_bfs_parent_fin");
+}
+
+}  // namespace
+}  // namespace gx
+
+using namespace gx;
+
+extern "C" int gx_bfs(gx_graph *g, uint64_t src, int64_t *level_out) {
+    if (!g || !level_out) return fail(GX_NULL_POINTER, "gx_bfs: null argument");
+    if (src >= g->n) return fail(GX_INVALID_INDEX, "gx_bfs: source out of range");
+    {
+        gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
+        GX_TRY(hub_for(g, ++g->hub_bfs_calls, &h, &src));
+        if (h) return gx_bfs(h, src, level_out);
+    }
+    BfsWork w;
     const void *res = nullptr;
-    GX_TRY(remap_out(g, level.p, 4, s, &res));
-    GX_TRY(device_end(ctx));
-    GX_TRY(download(ctx, level_out, res, (uint64_t)n, Xfer::Levels));
+    GX_TRY(bfs_levels(g, src, w, [&](bool, bool &queued) -> int {
+        queued = true;
+        return remap_out(g, w.level.p, 4, g->ctx->stream, &res);
+    }));
+    GX_TRY(device_end(g->ctx));
+    GX_TRY(download(g->ctx, level_out, res, g->n, Xfer::Levels));
+    return GX_SUCCESS;
+}
+
+extern "C" int gx_bfs_parent(gx_graph *g, uint64_t src, int64_t *level_out, int64_t *parent_out) {
+    if (!g || !parent_out) return fail(GX_NULL_POINTER, "gx_bfs_parent: null argument");
+    if (src >= g->n) return fail(GX_INVALID_INDEX, "gx_bfs_parent: source out of range");
+    {
+        gx_graph *h = nullptr;   // a parent call counts as a BFS call: the copy from the second
+        GX_TRY(hub_for(g, ++g->hub_bfs_calls, &h, &src));
+        if (h) return gx_bfs_parent(h, src, level_out, parent_out);
+    }
+    GX_HIP_TRY(hipSetDevice(g->ctx->device));
+    BfsWork w;
+    DBuf<int32_t> parent;
+    GX_TRY(parent.alloc(g->n));
+    const void *res_level = nullptr, *res_parent = nullptr;
+    // the parent pass reads finished levels and the loop's queue: never queued early
+    GX_TRY(bfs_levels(g, src, w, [&](bool early, bool &queued) -> int {
+        if (early) return GX_SUCCESS;
+        queued = true;
+        hipStream_t s = g->ctx->stream;
+        GX_TRY(bfs_parents(g, w, parent.p, s));
+        // on a copy the two results share remap_tmp: the levels its low 4-byte half, the parents its high
+        if (level_out) GX_TRY(remap_out(g, w.level.p, 4, s, &res_level, 0));
+        return remap_out(g, parent.p, 4, s, &res_parent, 1);
+    }));
+    GX_TRY(device_end(g->ctx));
+    if (level_out) GX_TRY(download(g->ctx, level_out, res_level, g->n, Xfer::Levels));
+    GX_TRY(download(g->ctx, parent_out, res_parent, g->n, Xfer::Sign32));
     return GX_SUCCESS;
 }
 

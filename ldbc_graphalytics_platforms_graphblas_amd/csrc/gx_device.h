@@ -161,7 +161,8 @@ int ensure_aux_streams(gx_ctx *ctx);
 int ensure_host_rp(gx_ctx *ctx, DevCSR &c);
 // Device -> host copy of `count` elements through the context's pinned staging buffers, the
 // conversion of each chunk (parallel, on the host) overlapping the next chunk's DMA.
-enum class Xfer { Raw64, Raw32, Levels, Widen32 };   // 8 / 4 B as is; int32 level -> int64 (INF); int32 -> uint64
+// 8 / 4 B as is; int32 level -> int64 (INF); int32 -> uint64; int32 -> int64 (sign kept: -1 = no parent)
+enum class Xfer { Raw64, Raw32, Levels, Widen32, Sign32 };
 int download(gx_ctx *ctx, void *dst, const void *src_dev, uint64_t count, Xfer kind);
 // Host -> device of `count` elements of `elem` bytes through the pinned staging buffers:
 // fill(off, cnt, buf) writes elements [off, off + cnt) into buf (false: bad input, *bad set).
@@ -272,7 +273,9 @@ struct KTimer {
 int hub_for(gx_graph *g, int calls, gx_graph **out, uint64_t *src);
 // The results to download: on a copy (g->out_perm set) buf scattered through out_order into
 // the parent's vertex order (g->remap_tmp; elem = 4 or 8 bytes, n entries), else buf itself.
-int remap_out(gx_graph *g, const void *buf, int elem, hipStream_t s, const void **res);
+// half = 1 (elem 4 only) lands in the second n 4-byte words of remap_tmp, so a call with two
+// 4-byte results keeps both there until they are downloaded.
+int remap_out(gx_graph *g, const void *buf, int elem, hipStream_t s, const void **res, int half = 0);
 
 // Collect elapsed times of finished timed launches into ctx->stats.
 int collect_timings(gx_ctx *ctx);

@@ -739,6 +739,11 @@ void host_widen(const int32_t *in, uint64_t n, uint64_t *out) {
     for (int64_t v = 0; v < (int64_t)n; v++) out[v] = (uint64_t)(uint32_t)in[v];
 }
 
+void host_sext(const int32_t *in, uint64_t n, int64_t *out) {
+#pragma omp parallel for schedule(static)
+    for (int64_t v = 0; v < (int64_t)n; v++) out[v] = (int64_t)in[v];
+}
+
 int host_chunk_columns(const uint64_t *ci, uint64_t nnz, const uint64_t *ranges, int nranks, const uint64_t *live,
                        uint64_t chunk, uint64_t n, int32_t *out) {
     int bad = 0;

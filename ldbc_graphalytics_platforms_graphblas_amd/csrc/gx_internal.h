@@ -28,6 +28,8 @@ bool host_monotone(const uint64_t *rp, uint64_t n);
 void host_levels(const int32_t *in, uint64_t n, int64_t *out);
 // labels: out[i] = (uint64) in[i]
 void host_widen(const int32_t *in, uint64_t n, uint64_t *out);
+// BFS parents: out[i] = (int64) in[i], sign-extended (-1 stays -1)
+void host_sext(const int32_t *in, uint64_t n, int64_t *out);
 // PageRank exchange layout: global column c of rank `owner` (ranges[owner] <= c < ranges[owner+1])
 // -> owner * chunk + (c - ranges[owner]); returns 0, or bit 0 = a column >= n, bit 1 = a column
 // past its owner's live rows

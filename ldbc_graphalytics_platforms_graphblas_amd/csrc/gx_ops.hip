@@ -9,6 +9,8 @@
 //   ANY_PAIR_BOOL      the BFS frontier vxm                             LAGr_BreadthFirstSearch, bfs.cpp:80
 //   MIN_PLUS_FP64      the SSSP relaxation vxm                          LAGr_SingleSourceShortestPath, sssp.cpp:78
 //   PLUS_PAIR_INT64    masked mxm C<A> = A A' (triangle counts)         LAGraph_lcc, lcc.cpp:68
+//   MIN_SECONDI_INT64  the parent BFS's vxm q<!pi> = q any.secondi A     LAGr_BreadthFirstSearch with a parent
+//                      (`any` resolved to `min`, as gx_bfs_parent does)
 //
 // mxv with PLUS_SECOND_FP64 over A' (the PageRank product) runs the headline kernel itself:
 // gx_pagerank's hub-first, column-sorted plan (k_pr_pull_units, gx_pr_sorted.hip) with damping
@@ -28,7 +30,9 @@ namespace {
 constexpr int kShortDeg = 64;
 constexpr int kSegNnz = 2048;
 
-enum Sr { kPlusSecondF64 = 0, kMinSecondU64 = 1, kAnyPairBool = 2, kMinPlusF64 = 3, kPlusPairI64 = 4 };
+enum Sr {
+    kPlusSecondF64 = 0, kMinSecondU64 = 1, kAnyPairBool = 2, kMinPlusF64 = 3, kPlusPairI64 = 4, kMinSecondiI64 = 5
+};
 
 template <int SR>
 struct Monoid;
@@ -77,9 +81,18 @@ struct Monoid<kPlusPairI64> {
     __device__ static T op(T a, T b) { return a + b; }
     __device__ static void atomic(T *p, T v) { atomicAdd(p, v); }
 };
+template <>
+struct Monoid<kMinSecondiI64> {
+    using T = long long;   // signed: ACCUM combines with whatever int64 the caller's w holds
+    __device__ static T id() { return INT64_MAX; }
+    __device__ static T op(T a, T b) { return a < b ? a : b; }
+    __device__ static void atomic(T *p, T v) { atomicMin(p, v); }
+};
 
 // The multiplicative op on (matrix value a, vector value u(j)): mxv takes mult(a, u), vxm
 // mult(u, a) (the matrix operand second); SECOND picks the second operand, PAIR is 1.
+// SECONDI is positional: the contracted index, which in a pull over the rows of M (A for mxv,
+// A' for vxm) is the entry's column j either way.
 // fp64 -> uint64 the way GraphBLAS typecasts (GB_cast_to_uint64_t): NaN and values <= 0 give
 // 0, values >= 2^64 give UINT64_MAX, the rest truncate.
 __device__ __forceinline__ unsigned long long cast_u64(double x) {
@@ -96,7 +109,8 @@ __device__ __forceinline__ typename Monoid<SR>::T term(double a, const void *u, 
     else if constexpr (SR == kMinPlusF64) {
         const double x = static_cast<const double *>(u)[j];
         return VXM ? x + a : a + x;
-    } else return 1ull;
+    } else if constexpr (SR == kMinSecondiI64) return (long long)j;
+    else return 1ull;
 }
 
 struct OpArgs {
@@ -192,7 +206,7 @@ __global__ __launch_bounds__(256) void k_op_finish(const void *tv, const uint8_t
                 continue;   // w(i) kept
             }
             T o;
-            if constexpr (SR == kPlusSecondF64 || SR == kMinPlusF64) o = (T)out[i];
+            if constexpr (SR == kPlusSecondF64 || SR == kMinPlusF64 || SR == kMinSecondiI64) o = (T)out[i];
             else o = (T)(unsigned long long)out[i];
             v = M::op(o, v);
         }
@@ -288,6 +302,9 @@ void launch_finish(const void *t, const uint8_t *hit, int64_t n, const uint8_t *
     else if constexpr (SR == kPlusSecondF64 || SR == kMinPlusF64)
         hipLaunchKernelGGL((k_op_finish<SR, double>), dim3(g), dim3(256), 0, s, t, hit, n, mask, desc,
                            static_cast<double *>(out), out_present);
+    else if constexpr (SR == kMinSecondiI64)
+        hipLaunchKernelGGL((k_op_finish<SR, long long>), dim3(g), dim3(256), 0, s, t, hit, n, mask, desc,
+                           static_cast<long long *>(out), out_present);
     else
         hipLaunchKernelGGL((k_op_finish<SR, unsigned long long>), dim3(g), dim3(256), 0, s, t, hit, n, mask, desc,
                            static_cast<unsigned long long *>(out), out_present);
@@ -296,7 +313,7 @@ void launch_finish(const void *t, const uint8_t *hit, int64_t n, const uint8_t *
 int op_vector(gx_graph *g, int sr, int vxm, int desc, const uint8_t *mask, const void *u, const uint8_t *u_present,
               void *out, uint8_t *out_present) {
     if (!g || !out) return fail(GX_NULL_POINTER, "gx_mxv/gx_vxm: null argument");
-    if (sr < 0 || sr > 4) return fail(GX_INVALID_VALUE, "gx_mxv/gx_vxm: unknown semiring");
+    if (sr < 0 || sr > kMinSecondiI64) return fail(GX_INVALID_VALUE, "gx_mxv/gx_vxm: unknown semiring");
     const bool needs_u = sr == kPlusSecondF64 ? !vxm : sr == kMinSecondU64 ? !vxm : sr == kMinPlusF64;
     if (needs_u && !u) return fail(GX_NULL_POINTER, "gx_mxv/gx_vxm: this semiring reads u");
     gx_ctx *ctx = g->ctx;
@@ -361,6 +378,7 @@ int op_vector(gx_graph *g, int sr, int vxm, int desc, const uint8_t *mask, const
             case 4: case 5: launch_rows<kAnyPairBool, false>(a, s); break;
             case 6: launch_rows<kMinPlusF64, false>(a, s); break;
             case 7: launch_rows<kMinPlusF64, true>(a, s); break;
+            case 10: case 11: launch_rows<kMinSecondiI64, false>(a, s); break;
             default: launch_rows<kPlusPairI64, false>(a, s); break;
         }
     }
@@ -370,6 +388,7 @@ int op_vector(gx_graph *g, int sr, int vxm, int desc, const uint8_t *mask, const
         case kMinSecondU64: launch_finish<kMinSecondU64>(t.p, hit.p, n, dmask.p, desc, dout.p, dop.p, s); break;
         case kAnyPairBool: launch_finish<kAnyPairBool>(t.p, hit.p, n, dmask.p, desc, dout.p, dop.p, s); break;
         case kMinPlusF64: launch_finish<kMinPlusF64>(t.p, hit.p, n, dmask.p, desc, dout.p, dop.p, s); break;
+        case kMinSecondiI64: launch_finish<kMinSecondiI64>(t.p, hit.p, n, dmask.p, desc, dout.p, dop.p, s); break;
         default: launch_finish<kPlusPairI64>(t.p, hit.p, n, dmask.p, desc, dout.p, dop.p, s); break;
     }
     GX_TRY(check_launch("k_op_finish"));

@@ -176,6 +176,9 @@ int download(gx_ctx *ctx, void *dst, const void *src_dev, uint64_t count, Xfer k
             case Xfer::Widen32:
                 host_widen(static_cast<const int32_t *>(buf), cnt, static_cast<uint64_t *>(dst) + off);
                 break;
+            case Xfer::Sign32:
+                host_sext(static_cast<const int32_t *>(buf), cnt, static_cast<int64_t *>(dst) + off);
+                break;
         }
     };
     uint64_t prev_off = 0, prev_cnt = 0;
@@ -713,11 +716,13 @@ int hub_for(gx_graph *g, int calls, gx_graph **out, uint64_t *src) {
     return GX_SUCCESS;
 }
 
-int remap_out(gx_graph *g, const void *buf, int elem, hipStream_t s, const void **res) {
+int remap_out(gx_graph *g, const void *buf, int elem, hipStream_t s, const void **res, int half) {
     *res = buf;
     if (!g->out_perm || !g->n) return GX_SUCCESS;
+    if (half && elem != 4) return fail(GX_INVALID_VALUE, "remap_out: the second half takes 4-byte results");
     const int64_t n = (int64_t)g->n;
-    void *tmp = g->remap_tmp.p;   // n words, allocated with the copy
+    // n 8-byte words, allocated with the copy; a 4-byte result fills either half of them
+    void *tmp = reinterpret_cast<uint32_t *>(g->remap_tmp.p) + (half ? n : 0);
     const unsigned grid = grid_for((uint64_t)n, 256, 8192);
     const char *re = std::getenv("GX_REMAP");
     if (!(re && std::strcmp(re, "scatter") == 0)) {
