@@ -99,10 +99,6 @@ struct SortedArgs {
     uint32_t pnull_sg;       // all-padding pair supergroup (base = the pair of zero_col)
     double *xd;              // x of the rows past `live` (store_x, gx_pr.h)
     int64_t live;
-    // paced sweep (PrPart::pace)
-    const int32_t *pace_rounds;
-    uint32_t *pace_prog;
-    uint32_t pace_nw, pace_d, pace_polls, pace_ncus;
     // work queue (GX_PR_QUEUE): [0] next work item, [1] workgroups done (reset by the last)
     uint32_t *queue;
     // combine kernel (PrPart::comb_kernel): the units of multi-unit blocks only store their slabs
@@ -249,28 +245,9 @@ __device__ __forceinline__ void long_segment(const SortedArgs &a, const RowBlock
 // columns of escape supergroups (spanning >= 2^18 ids) come from sci inside a uniform branch
 // that consumes its loads there: a load merged into the columns after the branch made the
 // compiler drain every outstanding load (s_waitcnt vmcnt(0)) each round.
-//
-// PROBE (diagnostic builds only, -DGX_PR_PROBES, tools/pr_probe.sh; wrong results by design):
-// 1 no LDS adds (register sum), 2 no gathers, 3 neither, 4 gathers folded into x[c & 4095]
-// (L1 hits), 5 no gathers + conflict-free LDS adds (acc[tid]), 6 gathers + conflict-free LDS
-// adds, 7 no index loads (entries synthesised from the position, columns = the base),
-// 8 gathers of columns >= 512 Ki folded into the first 512 Ki (the sparse tail as local as the
-// hub lines), 9 every gather folded into the first 64 Ki columns, 10 no entries at all (the
-// fixed costs: zeroing, epilogue, slabs), 11 as 3 (index loads and decode only).
-// gather_narrow takes all but 7 (which runs it unchanged); 12 (gather_narrow only) reads the
-// narrow entries' x from LDS (the accumulators at column mod 16 Ki): the launch if x came from
-// LDS instead of the texture path; 13 (gather_narrow only) two 16-B loads per lane per 8
-// entries (the instruction count of a layout loading each lane's column span once); 14
-// (gather_narrow only) only the first entry of each column run gathers, the rest read 0; 15 as 14
-// with the run's value handed on by ds_bpermute (correct results); 16 = the product kernel
-// under the probes' launch (no queue), the baseline for 12-15; 17 the wide entries (gather_units:
-// 4-byte packed entries and escapes) load and decode but do not gather (narrow unchanged), 18 no
-// wide entries at all (gather_units skipped): the wide tail's share of the launch (round 6);
-// 19 (gather_narrow only) four 16-B loads per lane and round at the aligned column pairs of
-// entries 0, 2, 4, 6, each feeding two adds (the ceiling of the pair slots, gather_pairs).
-template <int PROBE, int CP>   // CP bit 0: index loads non-temporal (bit 2: gather_narrow)
+template <int CP>   // CP bit 0: index loads non-temporal (bit 2: gather_narrow)
 __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock &b, int64_t lo64, int64_t hi64,
-                                             double *acc, int64_t step64, int32_t k0 = 0, int32_t k1 = 0x7fffffff) {
+                                             double *acc, int64_t step64) {
     const int tid = threadIdx.x;
     const int64_t z0 = b.nz_begin;
     const int32_t lo = (int32_t)(lo64 - z0), hi = (int32_t)(hi64 - z0), step = (int32_t)step64;
@@ -301,16 +278,11 @@ __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock
 #pragma unroll
         for (int v = 0; v < V; v++) {
             const int32_t sg = sg0 + v * 256;
-            if constexpr (PROBE == 7) {
-                const uint32_t e0 = (uint32_t)(sg + 4 * lane) & 4095u;
-                d.q[v] = make_uint4(e0, (e0 + 1) & 4095u, (e0 + 2) & 4095u, (e0 + 3) & 4095u);
-            } else {
-                // clamped into the block; spk's allocation slack covers the 3 entries past `last`;
-                // the address is a CSR offset, only 4-B aligned (gx_u32x4)
-                const gx_u32x4 *qa = reinterpret_cast<const gx_u32x4 *>(spk + min(sg + 4 * lane, last));
-                const gx_u32x4 q4 = (CP & 1) ? __builtin_nontemporal_load(qa) : *qa;
-                d.q[v] = make_uint4(q4.x, q4.y, q4.z, q4.w);
-            }
+            // clamped into the block; spk's allocation slack covers the 3 entries past `last`;
+            // the address is a CSR offset, only 4-B aligned (gx_u32x4)
+            const gx_u32x4 *qa = reinterpret_cast<const gx_u32x4 *>(spk + min(sg + 4 * lane, last));
+            const gx_u32x4 q4 = (CP & 1) ? __builtin_nontemporal_load(qa) : *qa;
+            d.q[v] = make_uint4(q4.x, q4.y, q4.z, q4.w);
         }
         d.bq = sgb[min((sg0 >> 8) + (lane & (V - 1)), nsg - 1)];
     };
@@ -335,11 +307,10 @@ __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock
                 // materialised here: sunk to the adds, the rows would keep this buffer's index
                 // registers live past its reload, and the allocator copies at the loop latch
                 asm volatile("" : "+v"(t.r[i]));
-                if constexpr (PROBE == 7) c[i] = ok ? (int32_t)base : zc;
-                else c[i] = ok ? (int32_t)(base + (w4[j] >> kRowBits)) : zc;
+                c[i] = ok ? (int32_t)(base + (w4[j] >> kRowBits)) : zc;
             }
         }
-        if (PROBE != 7 && (esc & 0x80000000u)) {   // uniform: an escape supergroup in this round
+        if (esc & 0x80000000u) {   // uniform: an escape supergroup in this round
 #pragma unroll
             for (int v = 0; v < V; v++) {
                 if (!(sb[v] & 0x80000000u)) continue;
@@ -355,33 +326,21 @@ __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock
             __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
         }
 #pragma unroll
-        for (int i = 0; i < kU; i++) {
-            if constexpr (PROBE == 2 || PROBE == 3 || PROBE == 5 || PROBE == 11 || PROBE == 17) t.g[i] = (double)c[i];
-            else if constexpr (PROBE == 4) t.g[i] = a.x_in[c[i] & 4095];
-            else if constexpr (PROBE == 8) t.g[i] = a.x_in[c[i] >= (1 << 19) ? (c[i] & ((1 << 19) - 1)) : c[i]];
-            else if constexpr (PROBE == 9) t.g[i] = a.x_in[c[i] & 65535];
-            else t.g[i] = *reinterpret_cast<const double *>(xb + ((uint32_t)c[i] << 3));
-        }
+        for (int i = 0; i < kU; i++) t.g[i] = *reinterpret_cast<const double *>(xb + ((uint32_t)c[i] << 3));
     };
-    double rsum = 0.0;   // PROBE 1 / 3
     auto add = [&](const Gt &t) {
 #pragma unroll
-        for (int i = 0; i < kU; i++) {
-            if constexpr (PROBE == 1 || PROBE == 3 || PROBE == 11) rsum += t.g[i];
-            else if constexpr (PROBE == 5 || PROBE == 6) atomicAdd(&acc[tid], t.g[i]);
-            else atomicAdd(&acc[t.r[i]], t.g[i]);
-        }
+        for (int i = 0; i < kU; i++) atomicAdd(&acc[t.r[i]], t.g[i]);
     };
     // Two rounds per trip of a counted loop with a single exit.  The stages are fenced from
     // the scheduler and the exits are not shared: a load hoisted above the issue that still
     // reads its buffer, or one exit block adding "tA or tB", makes the register allocator copy
     // a buffer at the loop latch, and a copy waits for the loads in flight.
-    // rounds [k0, k1) of this unit (a paced sweep's window; all of them by default)
-    const int32_t nr = min((hi - lo + step - 1) / step, k1) - k0;
+    const int32_t nr = (hi - lo + step - 1) / step;   // rounds of this unit
     if (nr <= 0) return;
     Rd dA, dB;
     Gt tA, tB;
-    int32_t R = lo + k0 * step;
+    int32_t R = lo;
     load(dA, R);
     load(dB, R + step);
     issue(dA, R, tA);
@@ -410,7 +369,6 @@ __device__ __forceinline__ void gather_units(const SortedArgs &a, const RowBlock
     } else {
         add(tA);
     }
-    if constexpr (PROBE == 1 || PROBE == 3 || PROBE == 11) atomicAdd(&acc[tid], rsum);
 }
 
 // Inclusive prefix sum over the 64 lanes by DPP moves (row_shr 1/2/4/8 inside each 16-lane
@@ -435,14 +393,12 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
 // null supergroup (padding codes, base = x's zero slot), so the loop has no range checks.
 // Same pipeline as gather_units: round i+1's gathers issue before round i's LDS adds, the
 // loads two rounds ahead, buffers A/B alternating.
-template <int CP, int PROBE = 0>
-__device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedUnit &u, double *acc, int32_t i0 = 0,
-                                              int32_t i1 = 0x7fffffff) {
+template <int CP>
+__device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedUnit &u, double *acc) {
     constexpr int W = kBS / kWave;   // supergroups per round
     const int32_t nrounds = (u.nsg + W - 1) / W;
     if (u.unit >= nrounds) return;
-    // rounds [i0, i1) of this unit (a paced sweep's window; all of them by default)
-    const int32_t nr = min((nrounds - u.unit + u.nunits - 1) / u.nunits, i1) - i0;
+    const int32_t nr = (nrounds - u.unit + u.nunits - 1) / u.nunits;   // rounds of this unit
     if (nr <= 0) return;
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -457,10 +413,9 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
     struct Gt {
         double g[kU];
         uint32_t r[kU];
-        uint64_t m[kU];   // PROBE 15: the leader mask of instruction k
     };
     auto load = [&](Rd &d, int32_t i) {
-        const int32_t sg = (u.unit + (i + i0) * u.nunits) * W + wave;
+        const int32_t sg = (u.unit + i * u.nunits) * W + wave;
         const uint32_t g = sg < u.nsg ? sg0 + (uint32_t)sg : a.null_sg;
         const u32x4 *qa = reinterpret_cast<const u32x4 *>(a.npk + (size_t)g * kNSg) + lane;
         d.q = (CP & 1) ? __builtin_nontemporal_load(qa) : *qa;
@@ -493,59 +448,7 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
             col[k] = bk + ((sk >> (8 * (k & 3))) & 255u);
             bk += (tk >> (8 * (k & 3))) & 255u;
         }
-        if constexpr (PROBE == 14 || PROBE == 15) {
-            // only the first entry of each column run gathers (a zero step repeats the previous
-            // sorted entry's column, lane 0 always loads): 14 leaves the others at 0, 15 hands the
-            // leader's value to them by ds_bpermute in the add stage (correct results)
-            const bool ntl = (CP & 4) && b0 >= a.nt_col;
-#pragma unroll
-            for (int k = 0; k < kU; k++) {
-                const uint32_t st = ((k < 4 ? pk[0] : pk[1]) >> (8 * (k & 3))) & 255u;
-                const bool lead = st != 0u || lane == 0;
-                if constexpr (PROBE == 15) t.m[k] = __builtin_amdgcn_ballot_w64(lead);
-                double v = 0.0;
-                if (lead) {
-                    const double *xp = reinterpret_cast<const double *>(xb + (col[k] << 3));
-                    v = ntl ? __builtin_nontemporal_load(xp) : *xp;
-                }
-                t.g[k] = v;
-            }
-        } else if constexpr (PROBE == 13) {
-            // two 16-B loads per lane instead of eight 8-B gathers: the instruction count of a
-            // layout whose lane loads its entries' column span once
-            typedef double d2 __attribute__((ext_vector_type(2)));
-            const d2 *x2 = reinterpret_cast<const d2 *>(a.x_in);
-            const uint32_t p0 = col[0] >> 1;
-            const d2 A = x2[p0], B = x2[p0 + 1];
-#pragma unroll
-            for (int k = 0; k < kU; k++) t.g[k] = (k & 3) == 0 ? A.x : (k & 3) == 1 ? A.y : (k & 3) == 2 ? B.x : B.y;
-            (void)b0;
-        } else if constexpr (PROBE == 19) {
-            // four 16-B loads per lane at the aligned pairs of columns 0, 2, 4, 6, each feeding two
-            // adds: half the gather instructions on the same lines, the ceiling of the pair slots
-            typedef double d2 __attribute__((ext_vector_type(2)));
-            const d2 *x2 = reinterpret_cast<const d2 *>(a.x_in);
-            const bool ntl = (CP & 4) && b0 >= a.nt_col;
-#pragma unroll
-            for (int k = 0; k < kU; k += 2) {
-                const d2 *xp = x2 + (col[k] >> 1);
-                const d2 v = ntl ? __builtin_nontemporal_load(xp) : *xp;
-                t.g[k] = v.x;
-                t.g[k + 1] = v.y;
-            }
-        } else if constexpr (PROBE == 2 || PROBE == 3 || PROBE == 5 || PROBE == 11 || PROBE == 4 || PROBE == 8 || PROBE == 9 ||
-                      PROBE == 12) {
-#pragma unroll
-            for (int k = 0; k < kU; k++) {
-                const uint32_t c = col[k];
-                if constexpr (PROBE == 2 || PROBE == 3 || PROBE == 5 || PROBE == 11) t.g[k] = (double)c;
-                else if constexpr (PROBE == 12) t.g[k] = acc[c & ((1u << kRowBits) - 1)];   // x from LDS
-                else if constexpr (PROBE == 4) t.g[k] = a.x_in[c & 4095u];
-                else if constexpr (PROBE == 8) t.g[k] = a.x_in[c >= (1u << 19) ? (c & ((1u << 19) - 1)) : c];
-                else t.g[k] = a.x_in[c & 65535u];
-            }
-            (void)b0;
-        } else if ((CP & 4) && b0 >= a.nt_col) {   // past the hub lines: streamed (GX_PR_CP bit 2)
+        if ((CP & 4) && b0 >= a.nt_col) {   // past the hub lines: streamed (GX_PR_CP bit 2)
 #pragma unroll
             for (int k = 0; k < kU; k++) t.g[k] = __builtin_nontemporal_load(reinterpret_cast<const double *>(xb + (col[k] << 3)));
         } else {
@@ -553,21 +456,9 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
             for (int k = 0; k < kU; k++) t.g[k] = *reinterpret_cast<const double *>(xb + (col[k] << 3));
         }
     };
-    double rsum = 0.0;   // PROBE 1 / 3 / 11: register sum instead of the LDS adds
-    const uint64_t lane_le = (2ull << lane) - 1;   // PROBE 15: lanes 0..lane
     auto add = [&](const Gt &t) {
 #pragma unroll
-        for (int k = 0; k < kU; k++) {
-            if constexpr (PROBE == 15) {
-                const int src = 63 - __builtin_clzll(t.m[k] & lane_le);   // bit 0 is always set
-                const uint64_t b = __builtin_bit_cast(uint64_t, t.g[k]);
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)b);
-                const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(b >> 32));
-                atomicAdd(&acc[t.r[k]], __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo));
-            } else if constexpr (PROBE == 1 || PROBE == 3 || PROBE == 11) rsum += t.g[k];
-            else if constexpr (PROBE == 5 || PROBE == 6) atomicAdd(&acc[threadIdx.x], t.g[k]);
-            else atomicAdd(&acc[t.r[k]], t.g[k]);
-        }
+        for (int k = 0; k < kU; k++) atomicAdd(&acc[t.r[k]], t.g[k]);
     };
     Rd dA, dB;
     Gt tA, tB;
@@ -598,7 +489,6 @@ __device__ __forceinline__ void gather_narrow(const SortedArgs &a, const SortedU
     } else {
         add(tA);
     }
-    if constexpr (PROBE == 1 || PROBE == 3 || PROBE == 11) atomicAdd(&acc[threadIdx.x], rsum);
 }
 
 // The pair prefix of a block: 4-byte slots of two entries whose columns lie in one 16-byte
@@ -707,47 +597,13 @@ __device__ __forceinline__ void gather_pairs(const SortedArgs &a, const SortedUn
     }
 }
 
-// Paced sweep (PrPart::pace): the CU slot of this workgroup inside its XCD (SE, SH, CU ids of
-// HW_REG_HW_ID bits 8..15) and the XCD's progress words (HW_REG_XCC_ID).  Placement is read,
-// not assumed; it only steers speed (cdna_hip_programming.md §1: never correctness).
-__device__ __forceinline__ uint32_t *pace_slot(const SortedArgs &a) {
-    const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;         // HW_REG_XCC_ID[3:0]
-    const uint32_t cu = (uint32_t)__builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4) & 255u;   // HW_REG_HW_ID[15:8]
-    return a.pace_prog + xcc * 256u + cu;
-}
-
-// Entering window `win` of generation `gen`: publish it, then wait (bounded: pace_polls polls)
-// until no unit of the same generation on this XCD is more than pace_d windows behind.  The
-// whole workgroup waits at the barriers; wave 0 polls the XCD's 256 slots with L1-bypassing
-// 16-B loads (L2-served; the slots are written with plain stores, which stay in L2).
-__device__ __forceinline__ void pace_wait(const SortedArgs &a, uint32_t *slot, uint32_t gen, uint32_t win) {
-    __syncthreads();
-    if (threadIdx.x < kWave) {
-        const uint32_t me = (gen << 16) | (win + 1);
-        if (threadIdx.x == 0) *reinterpret_cast<volatile uint32_t *>(slot) = me;
-        const gx_u32x4 *base = reinterpret_cast<const gx_u32x4 *>(a.pace_prog + (size_t)(slot - a.pace_prog) / 256 * 256);
-        for (uint32_t p = 0; p < a.pace_polls; p++) {
-            const gx_u32x4 q = __builtin_nontemporal_load(base + threadIdx.x);
-            const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
-            uint32_t lo = 0xffffu;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if ((w4[j] >> 16) == gen && (w4[j] & 0xffffu)) lo = min(lo, w4[j] & 0xffffu);
-            for (int off = 32; off > 0; off >>= 1) lo = min(lo, (uint32_t)__shfl_xor((int)lo, off, kWave));
-            if (win + 1 <= lo + a.pace_d) break;
-            __builtin_amdgcn_s_sleep(4);
-        }
-    }
-    __syncthreads();
-}
-
 // One iteration's SpMV over split blocks.  Work items: [0, nlong_pad) LONG row segments (padded
 // to a multiple of 8), then the units (largest first; the blocks of rows without entries last).  A multi-unit block's units store their row sums write-through (sc1) to
 // their own slab, drain them (vmcnt(0)) and take a ticket; the last arriver adds the slabs in
 // unit order with sc1 loads and runs the epilogue (MI355X_MICROARCH.md "Valid forms": sc1 stores
 // drained before the counter add, sc1 loads by the workgroup whose add came last).
 // TIMES: debug build with per-workgroup timestamps (GX_PR_UNIT_TIMES).
-template <bool TIMES, int PROBE, int CP, bool PACE>
+template <bool TIMES, int CP>
 __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w, double *acc, double *wred, int &last,
                                           const double teleport) {
     const int tid = threadIdx.x;
@@ -776,26 +632,9 @@ __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w,
     if (!empty) {
         for (int i = tid; i < nrows; i += kBS) acc[i] = 0.0;
         __syncthreads();
-        if constexpr (PACE) {
-            // window by window: the narrow rounds, then the wide rounds starting in it
-            const uint32_t nw = a.pace_nw;
-            const int32_t *pr = a.pace_rounds + (size_t)(w - a.nlong_pad) * 2 * (nw + 1);
-            uint32_t *slot = pace_slot(a);
-            const uint32_t gen = (w - a.nlong_pad) / a.pace_ncus;
-            for (uint32_t win = 0; win < nw; win++) {
-                const int32_t n0 = pr[win], n1 = pr[win + 1], w0 = pr[nw + 1 + win], w1 = pr[nw + 2 + win];
-                if (n0 == n1 && w0 == w1) continue;
-                pace_wait(a, slot, gen, win);
-                if (n1 > n0) gather_narrow<CP, PROBE>(a, u, acc, n0, n1);
-                if (w1 > w0) gather_units<PROBE, CP>(a, b, u.lo, u.hi, acc, u.step, w0, w1);
-            }
-            __syncthreads();
-            if (tid == 0) *reinterpret_cast<volatile uint32_t *>(slot) = 0u;   // this CU's sweep is over
-        } else if constexpr (PROBE != 10) {   // probe 10: no entries at all (the fixed costs)
-            gather_pairs<CP>(a, u, acc);   // (no paced form: a paced plan has no pair prefix)
-            gather_narrow<CP, PROBE>(a, u, acc);
-            if constexpr (PROBE != 18) gather_units<PROBE, CP>(a, b, u.lo, u.hi, acc, u.step);
-        }
+        gather_pairs<CP>(a, u, acc);
+        gather_narrow<CP>(a, u, acc);
+        gather_units<CP>(a, b, u.lo, u.hi, acc, u.step);
         __syncthreads();
     }
     if (TIMES && tid == 0) ts[1] = __builtin_amdgcn_s_memrealtime();
@@ -963,7 +802,7 @@ __device__ __forceinline__ uint32_t queue_fetch(uint32_t *q, uint32_t *slot) {
 // items from a device counter in the same order: the dispatcher deals workgroups to the XCDs
 // round-robin, so an item whose XCD has no free CU waits even while other XCDs idle; from a
 // queue every CU takes the next item the moment it is free.
-template <bool TIMES, int PROBE = 0, int CP = 0, bool PACE = false, bool QUEUE = false>
+template <bool TIMES, int CP = 0, bool QUEUE = false>
 __global__ __launch_bounds__(kBS, TIMES ? 1 : 4) void k_pr_pull_units(SortedArgs a) {
     extern __shared__ double acc[];
     __shared__ double wred[kBS / kWave];
@@ -972,14 +811,14 @@ __global__ __launch_bounds__(kBS, TIMES ? 1 : 4) void k_pr_pull_units(SortedArgs
     for (int k = 0; k < a.nranks; k++) dsum += a.x_in[(int64_t)k * a.chunk + a.chunk - 1];
     const double teleport = a.teleport0 + a.damping_over_n * dsum;
     if constexpr (!QUEUE) {
-        pull_item<TIMES, PROBE, CP, PACE>(a, blockIdx.x, acc, wred, last, teleport);
+        pull_item<TIMES, CP>(a, blockIdx.x, acc, wred, last, teleport);
     } else {
         __shared__ uint32_t item;
         const uint32_t total = a.nlong_pad + a.nunits;
         for (;;) {
             const uint32_t w = queue_fetch(a.queue, &item);   // (its barriers: the last item's LDS is free)
             if (w >= total) break;
-            pull_item<TIMES, PROBE, CP, PACE>(a, w, acc, wred, last, teleport);
+            pull_item<TIMES, CP>(a, w, acc, wred, last, teleport);
         }
         if (threadIdx.x == 0 &&
             __hip_atomic_fetch_add(&a.queue[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
@@ -987,6 +826,18 @@ __global__ __launch_bounds__(kBS, TIMES ? 1 : 4) void k_pr_pull_units(SortedArgs
             __hip_atomic_store(&a.queue[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+// The kernel of one launch, over one workgroup per item or (QUEUE) the resident workgroups of the
+// work queue.  The cache policy picks CP 5 or 1, any other value CP 0; the per-item stamps
+// (times, GX_PR_UNIT_TIMES) run without the cache policy.
+using PullKernel = void (*)(SortedArgs);
+template <bool QUEUE>
+PullKernel pull_kernel(bool times, int cache_policy) {
+    if (times) return k_pr_pull_units<true, 0, QUEUE>;
+    if (cache_policy == 5) return k_pr_pull_units<false, 5, QUEUE>;
+    if (cache_policy == 1) return k_pr_pull_units<false, 1, QUEUE>;
+    return k_pr_pull_units<false, 0, QUEUE>;
 }
 
 // The plan's one radix sort.  The rows are cut into segments, in row order: the sorted blocks
@@ -1504,49 +1355,6 @@ __global__ __launch_bounds__(256) void k_pair_emit(const RowBlock *__restrict__ 
     }
 }
 
-// Paced sweep plan: per unit, the first narrow round and the first wide round whose column is
-// in window w (window 0: columns below h; window w >= 1 from h + (w - 1) 2^wshift), w = 0..nw,
-// by binary searches over the unit's rounds (their first columns ascend).  One workgroup per unit.
-__global__ __launch_bounds__(64) void k_pace_rounds(const SortedUnit *__restrict__ units, uint32_t nunits,
-                                                    const uint32_t *__restrict__ nbase, const int32_t *__restrict__ sci,
-                                                    uint32_t nw, uint32_t h, uint32_t wshift, int32_t *__restrict__ out) {
-    const uint32_t ui = blockIdx.x;
-    if (ui >= nunits) return;
-    const SortedUnit u = units[ui];
-    int32_t *o = out + (size_t)ui * 2 * (nw + 1);
-    constexpr int W = kBS / kWave;
-    const int32_t nrounds = (u.nsg + W - 1) / W;
-    const int32_t nrn = u.unit >= nrounds ? 0 : (nrounds - u.unit + u.nunits - 1) / u.nunits;
-    const int32_t nrw = u.lo < u.hi ? (int32_t)((u.hi - u.lo + u.step - 1) / u.step) : 0;
-    const uint32_t sg0 = (uint32_t)(u.nbeg / kNSg);
-    for (uint32_t w = threadIdx.x; w <= nw; w += blockDim.x) {
-        int32_t rn = 0, rw = 0;
-        if (w == nw) {
-            rn = nrn;
-            rw = nrw;
-        } else if (w > 0) {
-            const uint64_t start = (uint64_t)h + ((uint64_t)(w - 1) << wshift);
-            int32_t L = 0, H = nrn;
-            while (L < H) {
-                const int32_t mid = (L + H) >> 1;
-                if ((uint64_t)nbase[sg0 + (uint32_t)((u.unit + mid * u.nunits) * W)] >= start) H = mid;
-                else L = mid + 1;
-            }
-            rn = L;
-            L = 0;
-            H = nrw;
-            while (L < H) {
-                const int32_t mid = (L + H) >> 1;
-                if ((uint64_t)(uint32_t)sci[u.lo + (int64_t)mid * u.step] >= start) H = mid;
-                else L = mid + 1;
-            }
-            rw = L;
-        }
-        o[w] = rn;
-        o[nw + 1 + w] = rw;
-    }
-}
-
 int env_int(const char *name, int dflt, int lo, int hi) {
     if (const char *e = std::getenv(name)) {
         const int v = std::atoi(e);
@@ -1762,17 +1570,15 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     p->ncodes = 0;
     p->nnarrow = 0;
     p->npair = p->npfill = p->npslots = 0;
-    // Pair slots (GX_PR_PAIRS; gather_pairs): off in a paced plan (GX_PR_PACE: its window table
-    // knows narrow and wide rounds only), which therefore keeps Q = 0 everywhere.  Every other
-    // mode (interleaved units, work queue, slab combine, GX_PR_COMBINE=1) takes the pair rounds
-    // as it takes the narrow ones.  The slots need an even chunk (a pair never straddles two
+    // Pair slots (GX_PR_PAIRS; gather_pairs).  Every mode (interleaved units, work queue, slab
+    // combine, GX_PR_COMBINE=1) takes the pair rounds as it takes the narrow ones.  The slots
+    // need an even chunk (a pair never straddles two
     // ranks' chunks, and x's zero slot chunk - 2 shares its pair with the dangling slot only).
     // On by default for a huge graph's single plan only, where it was measured to win (SYN-8_5,
     // alternated runs: 605.8-608.7 us per launch against 626.8-629.2 without); SYN-7_5 ran
     // 76.0-78.8 us against 72.9-73.7, and a block partition's pieces were not measured
     // (DESIGN.md 4).
-    const bool pairs_on =
-        env_int("GX_PR_PAIRS", huge && !piece ? 1 : 0, 0, 1) == 1 && env_int("GX_PR_PACE", 0, 0, 1) == 0;
+    const bool pairs_on = env_int("GX_PR_PAIRS", huge && !piece ? 1 : 0, 0, 1) == 1;
     if (pairs_on && (p->chunk & 1)) return fail(GX_INVALID_VALUE, "pr_plan_sorted: pair slots need an even chunk");
     // device temporaries of the plan, released after the unit-size search (which runs on the
     // host while the narrow codes and the lane permutation are built)
@@ -2209,27 +2015,6 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     p->queue_on = env_int("GX_PR_QUEUE", -1, -1, 1);
     GX_TRY(p->queue.alloc(2));
     GX_HIP_TRY(hipMemset(p->queue.p, 0, 2 * sizeof(uint32_t)));
-    // paced sweep (GX_PR_PACE=1; GX_PR_PACE_H first boundary column, GX_PR_PACE_W log2 window
-    // columns, GX_PR_PACE_D windows of lead, GX_PR_PACE_POLLS the bound on a wait)
-    p->pace = env_int("GX_PR_PACE", 0, 0, 1);
-    if (p->pace && p->nunits) {
-        const uint64_t ncols = p->nranks == 1 ? std::max<uint64_t>(p->n_global, 1) : p->chunk * (uint64_t)p->nranks;
-        p->pace_h = (uint32_t)env_int("GX_PR_PACE_H", 524288, 0, 1 << 30);
-        p->pace_wshift = (uint32_t)env_int("GX_PR_PACE_W", 18, 10, 30);
-        p->pace_d = (uint32_t)env_int("GX_PR_PACE_D", 1, 0, 1 << 14);
-        p->pace_polls = (uint32_t)env_int("GX_PR_PACE_POLLS", 64, 0, 1 << 20);
-        const uint64_t wcols = 1ull << p->pace_wshift;
-        p->pace_nw = 1 + (uint32_t)(ncols > p->pace_h ? (ncols - p->pace_h + wcols - 1) / wcols : 0);
-        if (p->pace_nw > 65000) p->pace_nw = 65000;
-        GX_TRY(p->pace_rounds.alloc((size_t)p->nunits * 2 * (p->pace_nw + 1)));
-        GX_TRY(p->pace_prog.alloc(8 * 256));
-        GX_HIP_TRY(hipMemsetAsync(p->pace_prog.p, 0, 8 * 256 * sizeof(uint32_t), p->ctx->stream));
-        hipLaunchKernelGGL(k_pace_rounds, dim3(p->nunits), dim3(64), 0, p->ctx->stream, p->units.p, p->nunits,
-                           p->nbase.p ? p->nbase.p : nullptr, p->sci.p, p->pace_nw, p->pace_h, p->pace_wshift,
-                           p->pace_rounds.p);
-        GX_TRY(check_launch("k_pace_rounds"));
-        GX_HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    }
     clk.mark("units");
     // fused dangling sum: every dangling row in a sorted block (none in a LONG block), one slot
     // per block holding dangling rows
@@ -2318,12 +2103,6 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
     // a pair slot's one load reads x[2p] and x[2p + 1]
     if (p->npair && (reinterpret_cast<uintptr_t>(x_full) & 15))
         return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots need x 16-byte aligned");
-    a.pace_rounds = p->pace_rounds.p;
-    a.pace_prog = p->pace_prog.p;
-    a.pace_nw = p->pace_nw;
-    a.pace_d = p->pace_d;
-    a.pace_polls = p->pace_polls;
-    a.pace_ncus = (uint32_t)std::max(1, p->ctx->num_cus);
     a.queue = p->queue.p;
     const char *times_path = std::getenv("GX_PR_UNIT_TIMES");   // debug: not under graph capture
     const uint32_t nw = p->nlong_pad + p->nunits;
@@ -2340,40 +2119,12 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
         const size_t lds = (size_t)(1 << kRowBits) * sizeof(double);
         const bool use_queue = p->queue_on == 1 || (p->queue_on == -1 && nw >= 2u * (unsigned)std::max(1, p->ctx->num_cus));
         const unsigned nq = std::min<unsigned>(nw, (unsigned)std::max(1, p->ctx->num_cus));
-        if (a.utimes) {
-            // (per-item stamps; the queued debug kernel runs without the cache policy)
-            if (use_queue) hipLaunchKernelGGL((k_pr_pull_units<true, 0, 0, false, true>), dim3(nq), dim3(kBS), lds, s, a);
-            else hipLaunchKernelGGL((k_pr_pull_units<true>), dim3(nw), dim3(kBS), lds, s, a);
-        } else {
-#ifdef GX_PR_PROBES
-            if (const char *pe = std::getenv("GX_PR_PROBE")) {
-                switch (std::atoi(pe)) {
-// the probes run under the plan's cache policy (0, or 5 for a large x)
-#define GX_PROBE_CASE(k) case k: if (p->cache_policy == 5) hipLaunchKernelGGL((k_pr_pull_units<false, k, 5>), dim3(nw), dim3(kBS), lds, s, a); \
-                                 else hipLaunchKernelGGL((k_pr_pull_units<false, k>), dim3(nw), dim3(kBS), lds, s, a); break;
-                GX_PROBE_CASE(1) GX_PROBE_CASE(2) GX_PROBE_CASE(3) GX_PROBE_CASE(4) GX_PROBE_CASE(5) GX_PROBE_CASE(6) GX_PROBE_CASE(7)
-                GX_PROBE_CASE(8) GX_PROBE_CASE(9) GX_PROBE_CASE(10) GX_PROBE_CASE(11) GX_PROBE_CASE(12)
-                GX_PROBE_CASE(13) GX_PROBE_CASE(14) GX_PROBE_CASE(15) GX_PROBE_CASE(16) GX_PROBE_CASE(17) GX_PROBE_CASE(18) GX_PROBE_CASE(19)
-#undef GX_PROBE_CASE
-                default: hipLaunchKernelGGL((k_pr_pull_units<false>), dim3(nw), dim3(kBS), lds, s, a);
-                }
-            } else
-#endif
-            // (narrow gathers three rounds deep ran the same: SYN-8_5 752-753 against 753-754
-            // us, SYN-7_5 72.1-73.2 against 71.5-72.4; tools/r03_depth_ab.sh)
-            if (p->pace && p->nunits) {
-                if (p->cache_policy == 5) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 5, true>), dim3(nw), dim3(kBS), lds, s, a);
-                else if (p->cache_policy == 1) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 1, true>), dim3(nw), dim3(kBS), lds, s, a);
-                else hipLaunchKernelGGL((k_pr_pull_units<false, 0, 0, true>), dim3(nw), dim3(kBS), lds, s, a);
-            } else if (use_queue) {
-                // one resident workgroup per CU (the LDS allows no second), never more than the items
-                if (p->cache_policy == 5) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 5, false, true>), dim3(nq), dim3(kBS), lds, s, a);
-                else if (p->cache_policy == 1) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 1, false, true>), dim3(nq), dim3(kBS), lds, s, a);
-                else hipLaunchKernelGGL((k_pr_pull_units<false, 0, 0, false, true>), dim3(nq), dim3(kBS), lds, s, a);
-            } else if (p->cache_policy == 5) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 5>), dim3(nw), dim3(kBS), lds, s, a);
-            else if (p->cache_policy == 1) hipLaunchKernelGGL((k_pr_pull_units<false, 0, 1>), dim3(nw), dim3(kBS), lds, s, a);
-            else hipLaunchKernelGGL((k_pr_pull_units<false>), dim3(nw), dim3(kBS), lds, s, a);
-        }
+        // (narrow gathers three rounds deep ran the same: SYN-8_5 752-753 against 753-754
+        // us, SYN-7_5 72.1-73.2 against 71.5-72.4; tools/r03_depth_ab.sh)
+        const PullKernel k = use_queue ? pull_kernel<true>(a.utimes != nullptr, p->cache_policy)
+                                       : pull_kernel<false>(a.utimes != nullptr, p->cache_policy);
+        // queued: one resident workgroup per CU (the LDS allows no second), never more than the items
+        hipLaunchKernelGGL(k, dim3(use_queue ? nq : nw), dim3(kBS), lds, s, a);
         // (inside the iteration's timer: the SpMV is both launches)
         if (p->ncstripes) hipLaunchKernelGGL(k_pr_combine, dim3(p->ncstripes), dim3(kCombBS), 0, s, a);
         if (a.utimes && ++p->utimes_launch == env_int("GX_PR_UNIT_TIMES_LAUNCH", 5, 1, 1 << 30)) {

@@ -220,11 +220,8 @@ def test_pagerank_long_row_segments(ctx, monkeypatch, laneperm):
                                   "GX_PR_BLOCK_NNZ": "65536", "GX_PR_LONG_NNZ": "1024"},
                                  {"GX_PR_QUEUE": "1", "GX_PR_UNIT_NNZ": "1024", "GX_PR_BLOCK_NNZ": "8192",
                                   "GX_PR_LONG_NNZ": "1024", "GX_PR_CP": "5", "GX_PR_NT_COL": "1000"},
-                                 {"GX_PR_PACE": "1", "GX_PR_PACE_H": "1024", "GX_PR_PACE_W": "10"},
-                                 {"GX_PR_PACE": "1", "GX_PR_PACE_H": "0", "GX_PR_PACE_W": "11", "GX_PR_PACE_D": "0",
-                                  "GX_PR_UNIT_NNZ": "8192", "GX_PR_BLOCK_NNZ": "65536"},
-                                 {"GX_PR_PACE": "1", "GX_PR_PACE_H": "4096", "GX_PR_PACE_W": "12", "GX_PR_CP": "5",
-                                  "GX_PR_NT_COL": "1000", "GX_PR_UNIT_NNZ": "8192", "GX_PR_BLOCK_NNZ": "524288"}])
+                                 pytest.param({"GX_PR_CP": "5", "GX_PR_NT_COL": "1000", "GX_PR_UNIT_NNZ": "8192",
+                                               "GX_PR_BLOCK_NNZ": "524288"}, id="cp5_nt_col_units")])
 def test_pagerank_plan_variants(ctx, monkeypatch, env):
     """The default plan, non-temporal index loads and sparse narrow gathers (GX_PR_CP=1 / 5, the large-graph default), the plan's key sort in groups of two segments or with 64-bit keys, without the lane permutation, blocks cut into many units, tiny blocks, 16 Ki- / 2 Ki- / 64-row blocks, split
     blocks (several workgroups per sorted block, combined through slabs by the last arriver, or

@@ -21,7 +21,7 @@ at least 4 of the block's entries.  --quads also prints the four-entry slots of 
 for the prefix rules (a follow-up, not built).
 
 These are counts, not times: what a removed gather instruction is worth is measured on the GPU
-(probe 19 of tools/pr_probe.sh, and the A/B runs of GX_PR_PAIRS in DESIGN.md 4).
+(timing probe 19, since removed, and the A/B runs of GX_PR_PAIRS, both in DESIGN.md 4).
 
 python tools/pr_pair_model.py [scale edgefactor seed] [--rows R] [--block B] [--quads]
 (default 23 40 85: SYN-8_5, about 40 GB of host memory; 20 32 75 --rows 4096 --block 1048576: SYN-7_5)"""
