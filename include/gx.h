@@ -128,6 +128,24 @@ int gx_bfs(gx_graph *g, uint64_t src, int64_t *level);
  * the edges derives the parents from them.  Counts as a BFS call on g (transpose, copy). */
 int gx_bfs_parent(gx_graph *g, uint64_t src, int64_t *level, int64_t *parent);
 
+/* The role of LAGr_Betweenness(&centrality, G, sources, ns): Brandes' dependency accumulation from a
+ * batch of sources, one after the other.  For a source s, with hop levels over out-edges as gx_bfs
+ * gives them: sigma_s(s) = 1, sigma_s(v) = sum of sigma_s(u) over stored A(u,v) with level[u] ==
+ * level[v] - 1 (the number of shortest s -> v paths; 0 when v is unreachable), and delta_s(u) = sum
+ * over stored A(u,w) with level[w] == level[u] + 1 of sigma_s(u) / sigma_s(w) * (1 + delta_s(w)).
+ * centrality[v] = sum of delta_s(v) over the sources s != v in the order given: a source's own
+ * traversal adds nothing to its own entry (Brandes' rule; what LAGraph leaves in the sources' own
+ * entries is not claimed here).  A source listed twice counts twice; ns == 0 gives zeros.  Edge
+ * weights are ignored.  On an undirected graph both stored directions are edges and nothing is
+ * halved: with every vertex a source the result is twice the usual undirected value.
+ * paths may be NULL; else ns * n doubles, row k = sigma of sources[k].  sigma is held in fp64 and
+ * is exact while below 2^53.  No floating-point atomics: every sum has a fixed order, so a result
+ * is the same bit for bit on every run, and does not depend on how the levels were traversed.
+ * NULL g or centrality, or NULL sources with ns > 0: GX_NULL_POINTER; a source >= n:
+ * GX_INVALID_INDEX; both before any device work, the outputs untouched.  Always runs on g itself
+ * (never the hub-first copy); builds and caches the transpose of a directed graph. */
+int gx_betweenness(gx_graph *g, const uint64_t *sources, uint64_t ns, double *centrality, double *paths);
+
 /* LAGr_PageRankGX(&r, &iters, G, damping, itermax) incl. LAGraph_Cached_OutDegree /
  * LAGraph_Cached_AT (pr.cpp:58-61).  Graphalytics PR with dangling redistribution,
  * exactly `iters` iterations, fp64. */

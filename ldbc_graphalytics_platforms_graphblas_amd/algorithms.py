@@ -114,6 +114,24 @@ def LA_BFS_parent(G: Graph, source_vertex: int):
     return level, parent
 
 
+# gx_betweenness's row tiers (gx_bfs.hip kBcShort / kBcLong): a row of at most BC_SHORT entries is
+# one thread's, of at most BC_LONG one wave's, a longer one a workgroup's; GX_BC_SHORT / GX_BC_LONG override.
+# GX_BC_BITS: rows a level bucket needs to probe a level bitmap instead of the levels (0 always, -1 never)
+BC_SHORT, BC_LONG = 32, 2048
+
+
+def LA_BC(G: Graph, sources, return_paths: bool = False):
+    """The role of LAGr_Betweenness (gx_betweenness): Brandes' dependencies summed over the batch
+    `sources`, float64[n]; with return_paths also paths[ns, n], row k the shortest-path counts
+    from sources[k].  A source's own traversal adds nothing to its own entry."""
+    src = np.ascontiguousarray(sources, dtype=np.uint64).reshape(-1)
+    out = np.zeros(G.n, dtype=np.float64)
+    paths = np.zeros((len(src), G.n), dtype=np.float64) if return_paths else None
+    N.check(N.lib().gx_betweenness(G.handle, N.as_u64p(src) if len(src) else None, len(src), N.as_dp(out),
+                                   N.as_dp(paths) if return_paths else None), "gx_betweenness")
+    return (out, paths) if return_paths else out
+
+
 def LA_PR(G: Graph, damping_factor: float, iteration_num: int) -> np.ndarray:
     """pr.cpp:47-66: Graphalytics PageRank, fp64."""
     out = np.empty(G.n, dtype=np.float64)

@@ -13,8 +13,10 @@
 // unique, so the result is bit-exact whatever the traversal order.
 // gx_bfs_parent (LAGr_BreadthFirstSearch with its parent output) runs the same levels, then one
 // pass over the edges that gives every reached vertex its smallest parent (below, "parents").
+#include <algorithm>
 #include <cstdlib>
 #include <memory>
+#include <vector>
 
 #include "gx_device.h"
 
@@ -571,9 +573,10 @@ struct BfsWork {
 // caller ends the bracket.  tail(early) queues the caller's work behind the last level (the
 // results' remap, the parent pass) and returns whether it did: with early set it is queued
 // behind the levels expected to be the last, before the host knows they are, and is asked for
-// again if they were not.
+// again if they were not.  bracket = false: the caller has opened the device bracket itself
+// (gx_betweenness: one bracket over a batch of sources).
 template <typename Tail>
-int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail) {
+int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail, bool bracket = true) {
     gx_ctx *ctx = g->ctx;
     GX_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -587,16 +590,18 @@ int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail) {
     DBuf<unsigned long long> &nedges = w.nedges;
     DBuf<uint64_t> &fbits = w.fbits;
     DBuf<unsigned long long> &bucnt = w.bucnt;
-    GX_TRY(fbits.alloc(2 * ((n + 63) / 64)));   // two bitmaps: the device-driven path alternates them
+    // a work set that already served a BFS of this graph (gx_betweenness: one per batch) keeps its buffers
+    auto sized = [](auto &buf, size_t count) -> int { return buf.p && buf.n == count ? GX_SUCCESS : buf.alloc(count); };
+    GX_TRY(sized(fbits, 2 * ((n + 63) / 64)));   // two bitmaps: the device-driven path alternates them
     uint64_t *const fb1 = fbits.p + (n + 63) / 64;
-    GX_TRY(bucnt.alloc(2));
+    GX_TRY(sized(bucnt, 2));
     const uint64_t qcap = (uint64_t)n + g->nnz / kChunk + 64;   // sum over vertices of ceil(deg / kChunk)
-    GX_TRY(level.alloc(n));
-    GX_TRY(q0.alloc(qcap));
-    GX_TRY(q1.alloc(qcap));
-    GX_TRY(qcount.alloc(1));
-    GX_TRY(nedges.alloc(1));
-    GX_TRY(device_begin(ctx));
+    GX_TRY(sized(level, n));
+    GX_TRY(sized(q0, qcap));
+    GX_TRY(sized(q1, qcap));
+    GX_TRY(sized(qcount, 1));
+    GX_TRY(sized(nedges, 1));
+    if (bracket) GX_TRY(device_begin(ctx));
     // in-edges: the graph itself when undirected; for a directed graph the transpose, built on
     // the device and cached once the graph serves a second BFS (a one-off run, like the
     // Graphalytics executable's, would not win back the build).  GX_BFS_TRANSPOSE = 0 never,
@@ -616,7 +621,7 @@ int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail) {
         // device-driven levels (k_bfs_plan), queued in batches; the done flag is read one
         // batch late
         DBuf<BfsState> &st = w.st;
-        GX_TRY(st.alloc(1));
+        GX_TRY(sized(st, 1));
         BfsState h{};
         const int64_t dsrc = src_deg;
         h.have_queue = 1;
@@ -638,12 +643,16 @@ int bfs_levels(gx_graph *g, uint64_t src, BfsWork &w, Tail &&tail) {
         hipLaunchKernelGGL(k_bfs_seed, dim3(1), dim3(256), 0, s, g->A.rp.p, level.p, q0.p, &st.p->qcnt[0],
                            (int32_t)src);
         GX_TRY(check_launch("k_bfs_seed"));
-        int32_t *h_done = nullptr;
-        hipEvent_t ev = nullptr;
-        GX_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_done), 4 * sizeof(int32_t), hipHostMallocDefault));
-        w.done_guard.reset(h_done);
-        GX_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        w.ev_guard.reset(ev);
+        int32_t *h_done = w.done_guard.get();
+        hipEvent_t ev = w.ev_guard.get();
+        if (!h_done) {
+            GX_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_done), 4 * sizeof(int32_t), hipHostMallocDefault));
+            w.done_guard.reset(h_done);
+        }
+        if (!ev) {
+            GX_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            w.ev_guard.reset(ev);
+        }
         // grids of the kernels that run idle on the levels of the other direction: an idle
         // 8192-workgroup launch cost 2.6-3.0 us, a 2048 one 0.9 (r04_bfs_kernel_stats.csv);
         // every kernel is a grid-stride loop (GX_BFS_GRID overrides)
@@ -830,6 +839,373 @@ int bfs_parents(gx_graph *g, BfsWork &w, int32_t *parent, hipStream_t s) {
     return check_launch("k_bfs_parent_fin");
 }
 
+// ---- betweenness centrality (gx_betweenness) ---------------------------------------------
+// Brandes' algorithm, one source after the other, on the finished levels of bfs_levels:
+//   buckets : the reached vertices counting-sorted by (level, row tier) into one n-word order
+//             array (k_bc_bucket: histogram, k_bc_scan, k_bc_bucket again as the scatter), so a
+//             per-level launch touches that level's vertices only and each tier gets a launch
+//             of its own, sized on the host from the offsets.  Positions inside a bucket come
+//             from integer atomics and differ run to run; no value depends on them.
+//   sigma   : d = 1..depth, every v in bucket d pulls sigma[u] over its in-row, level[u] == d - 1.
+//   delta   : d = depth-1..1, every u in bucket d pulls coef[w] = (1 + delta[w]) / sigma[w] over
+//             its out-row, level[w] == d + 1, times sigma[u]; the same thread adds it to
+//             centrality[u] and leaves coef[u] (level 0 holds the source alone, whose own entry
+//             takes nothing).
+//   probes  : a bucket of at least GX_BC_BITS rows (kBcBitsRows) tests "x is at the level pulled
+//             from" in a bitmap of that level, set and cleared from that level's bucket; a
+//             smaller one reads level[x].  Both see the same edges in the same order.
+// A row is one thread's (at most GX_BC_SHORT entries), one wave's (at most GX_BC_LONG) or one
+// workgroup's; the lane of an entry depends on its offset in the row alone and the partial sums
+// meet in a fixed tree, so no floating-point atomic is needed and a result is the same bit for
+// bit on every run.
+constexpr int kBcShort = 32;    // GX_BC_SHORT overrides
+constexpr int kBcLong = 2048;   // GX_BC_LONG overrides
+constexpr uint32_t kBcBins = 768;   // (level, tier) keys counted in LDS: the first 256 levels
+constexpr int64_t kBcTile = 4096;   // vertices per workgroup step of the bucket kernels
+constexpr uint32_t kBcBitsRows = 1024;   // a bucket of this many rows probes a level bitmap (GX_BC_BITS overrides)
+
+__global__ __launch_bounds__(kBfsBlock) void k_bc_depth(const int32_t *__restrict__ level, int64_t n,
+                                                        int32_t *maxlevel) {
+    int32_t m = 0;
+    for (int64_t v = (int64_t)blockIdx.x * kBfsBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBfsBlock)
+        m = max(m, level[v]);
+    for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0 && m > 0) atomicMax(maxlevel, m);
+}
+
+// key of v: 3 * level + tier of its row in rp; nk (no bucket) when unreached
+__device__ __forceinline__ uint32_t bc_key(const int32_t *__restrict__ level, const int64_t *__restrict__ rp,
+                                           int64_t v, int32_t maxlevel, int sh, int lg, uint32_t nk) {
+    const int32_t lv = level[v];
+    if (lv < 0 || lv > maxlevel) return nk;
+    const int64_t len = rp[v + 1] - rp[v];
+    return 3u * (uint32_t)lv + (len <= sh ? 0u : (len <= lg ? 1u : 2u));
+}
+
+// SCATTER = false: cnt[key] += the vertices of each key.  SCATTER = true: cnt holds each key's
+// running position (its exclusive offset at the start); order[position] = v.  A tile's keys are
+// counted in LDS first, so a level's thousands of vertices cost one global atomic per tile.
+template <bool SCATTER>
+__global__ __launch_bounds__(kBfsBlock) void k_bc_bucket(const int32_t *__restrict__ level,
+                                                         const int64_t *__restrict__ rp, int64_t n,
+                                                         int32_t maxlevel, int sh, int lg, uint32_t *cnt,
+                                                         int32_t *order) {
+    __shared__ uint32_t bins[kBcBins];
+    const uint32_t nk = 3u * (uint32_t)(maxlevel + 1);
+    const uint32_t nb = min(nk, kBcBins);
+    for (int64_t t0 = (int64_t)blockIdx.x * kBcTile; t0 < n; t0 += (int64_t)gridDim.x * kBcTile) {
+        const int64_t t1 = min(t0 + kBcTile, n);
+        for (uint32_t b = threadIdx.x; b < nb; b += kBfsBlock) bins[b] = 0;
+        __syncthreads();
+        for (int64_t v = t0 + threadIdx.x; v < t1; v += kBfsBlock) {
+            const uint32_t key = bc_key(level, rp, v, maxlevel, sh, lg, nk);
+            if (key < nb) atomicAdd(&bins[key], 1u);
+            else if (!SCATTER && key < nk) atomicAdd(&cnt[key], 1u);
+        }
+        __syncthreads();
+        for (uint32_t b = threadIdx.x; b < nb; b += kBfsBlock) {
+            const uint32_t c = bins[b];
+            if (c) {
+                const uint32_t base = atomicAdd(&cnt[b], c);
+                if (SCATTER) bins[b] = base;
+            }
+        }
+        if constexpr (SCATTER) {
+            __syncthreads();
+            for (int64_t v = t0 + threadIdx.x; v < t1; v += kBfsBlock) {
+                const uint32_t key = bc_key(level, rp, v, maxlevel, sh, lg, nk);
+                if (key >= nk) continue;
+                const uint32_t pos = key < nb ? atomicAdd(&bins[key], 1u) : atomicAdd(&cnt[key], 1u);
+                if ((int64_t)pos < n) order[pos] = (int32_t)v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// One workgroup: off[0..nk] = exclusive scan of cnt[0..nk), and cnt becomes the scatter's cursors.
+__global__ __launch_bounds__(kBfsBlock) void k_bc_scan(uint32_t *cnt, uint32_t *off, uint32_t nk) {
+    __shared__ uint32_t wsum[kBfsBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    uint32_t carry = 0;
+    for (uint32_t i0 = 0; i0 < nk; i0 += kBfsBlock) {
+        const uint32_t i = i0 + threadIdx.x;
+        const uint32_t c = i < nk ? cnt[i] : 0u;
+        uint32_t x = c;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, kWave);
+            if (lane >= o) x += y;
+        }
+        if (lane == kWave - 1) wsum[w] = x;
+        __syncthreads();
+        uint32_t before = 0, step = 0;
+        for (int j = 0; j < kBfsBlock / kWave; j++) {
+            if (j < w) before += wsum[j];
+            step += wsum[j];
+        }
+        if (i < nk) {
+            const uint32_t excl = carry + before + x - c;
+            off[i] = excl;
+            cnt[i] = excl;
+        }
+        carry += step;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[nk] = carry;
+}
+
+__global__ void k_bc_seed(double *sigma, double *coef, int32_t src) {
+    sigma[src] = 1.0;
+    coef[src] = 1.0;
+}
+
+// The bits of a bucket's vertices in the level bitmap: set (integer atomicOr) before the pulls
+// that probe that level, cleared word by word after them, so the cost follows the bucket and
+// never n.
+__global__ __launch_bounds__(kBfsBlock) void k_bc_bits(const int32_t *__restrict__ order, uint32_t count,
+                                                       unsigned long long *fb, int set) {
+    for (uint32_t i = blockIdx.x * kBfsBlock + threadIdx.x; i < count; i += gridDim.x * kBfsBlock) {
+        const int32_t v = order[i];
+        if (set) atomicOr(&fb[v >> 6], 1ull << (v & 63));
+        else fb[v >> 6] = 0ull;
+    }
+}
+
+// Four entries of a row, `step` apart from k (k < e): the four membership probes issue before any
+// is tested; val[x] is gathered for the x at level lv1 only.  BITS: the probe reads the bitmap of
+// that level (n/8 bytes, L2-resident: the bottom-up BFS's argument) instead of level[x].
+template <bool BITS>
+__device__ __forceinline__ double bc_quad(const int32_t *__restrict__ ci, const int32_t *__restrict__ level,
+                                          const unsigned long long *__restrict__ fb, const double *val, int64_t k,
+                                          int64_t step, int64_t e, int32_t lv1) {
+    const int64_t last = e - 1;
+    const int64_t k1 = k + step, k2 = k + 2 * step, k3 = k + 3 * step;
+    const int32_t x0 = ci[k];
+    const int32_t x1 = ci[min(k1, last)];
+    const int32_t x2 = ci[min(k2, last)];
+    const int32_t x3 = ci[min(k3, last)];
+    bool h0, h1, h2, h3;
+    if constexpr (BITS) {
+        const unsigned long long w0 = fb[x0 >> 6], w1 = fb[x1 >> 6], w2 = fb[x2 >> 6], w3 = fb[x3 >> 6];
+        h0 = (w0 >> (x0 & 63)) & 1ull;
+        h1 = (w1 >> (x1 & 63)) & 1ull;
+        h2 = (w2 >> (x2 & 63)) & 1ull;
+        h3 = (w3 >> (x3 & 63)) & 1ull;
+    } else {
+        const int32_t l0 = level[x0], l1 = level[x1], l2 = level[x2], l3 = level[x3];
+        h0 = l0 == lv1;
+        h1 = l1 == lv1;
+        h2 = l2 == lv1;
+        h3 = l3 == lv1;
+    }
+    const double t0 = h0 ? val[x0] : 0.0;
+    const double t1 = (h1 && k1 < e) ? val[x1] : 0.0;
+    const double t2 = (h2 && k2 < e) ? val[x2] : 0.0;
+    const double t3 = (h3 && k3 < e) ? val[x3] : 0.0;
+    return (t0 + t1) + (t2 + t3);
+}
+
+// coef[w] = (1 + delta[w]) / sigma[w], what a parent u of w adds to delta[u] / sigma[u]: one
+// division per vertex, when its delta is final (1 / sigma[w] until then: delta = 0 at the deepest
+// level), and one gather per tree edge in the delta pull.  delta itself is never stored.
+template <bool BACK>
+__device__ __forceinline__ void bc_store(double acc, int32_t v, double *sigma, double *coef, double *cent) {
+    if constexpr (BACK) {
+        const double sg = sigma[v], d = sg * acc;
+        coef[v] = (1.0 + d) / sg;
+        cent[v] += d;
+    } else {
+        sigma[v] = acc;
+        coef[v] = 1.0 / acc;
+    }
+}
+
+// One thread per row of the bucket order[0..count).
+template <bool BACK, bool BITS>
+__global__ __launch_bounds__(kBfsBlock) void k_bc_rows(const int64_t *__restrict__ rp,
+                                                       const int32_t *__restrict__ ci,
+                                                       const int32_t *__restrict__ level,
+                                                       const unsigned long long *__restrict__ fb,
+                                                       const int32_t *__restrict__ order, uint32_t count,
+                                                       int32_t lv1, double *sigma, double *coef, double *cent) {
+    const double *val = BACK ? coef : sigma;
+    for (uint32_t i = blockIdx.x * kBfsBlock + threadIdx.x; i < count; i += gridDim.x * kBfsBlock) {
+        const int32_t v = order[i];
+        const int64_t b = rp[v], e = rp[v + 1];
+        double acc = 0.0;
+        for (int64_t k = b; k < e; k += 4) acc += bc_quad<BITS>(ci, level, fb, val, k, 1, e, lv1);
+        bc_store<BACK>(acc, v, sigma, coef, cent);
+    }
+}
+
+// One wave per row: lane l takes the entries l, l + 64, ... of the row, then a fixed xor tree.
+template <bool BACK, bool BITS>
+__global__ __launch_bounds__(kBfsBlock) void k_bc_wave(const int64_t *__restrict__ rp,
+                                                       const int32_t *__restrict__ ci,
+                                                       const int32_t *__restrict__ level,
+                                                       const unsigned long long *__restrict__ fb,
+                                                       const int32_t *__restrict__ order, uint32_t count,
+                                                       int32_t lv1, double *sigma, double *coef, double *cent) {
+    const double *val = BACK ? coef : sigma;
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = (blockIdx.x * kBfsBlock + threadIdx.x) / kWave;
+    const uint32_t nwaves = gridDim.x * (kBfsBlock / kWave);
+    for (uint32_t i = wave; i < count; i += nwaves) {
+        const int32_t v = order[i];
+        const int64_t b = rp[v], e = rp[v + 1];
+        double acc = 0.0;
+        for (int64_t k = b + lane; k < e; k += 4 * kWave) acc += bc_quad<BITS>(ci, level, fb, val, k, kWave, e, lv1);
+        acc = wave_sum(acc);
+        if (lane == 0) bc_store<BACK>(acc, v, sigma, coef, cent);
+    }
+}
+
+// One workgroup per row: thread t takes the entries t, t + 256, ...; each wave's xor tree, then
+// the four wave sums from LDS in a fixed order.
+template <bool BACK, bool BITS>
+__global__ __launch_bounds__(kBfsBlock) void k_bc_block(const int64_t *__restrict__ rp,
+                                                        const int32_t *__restrict__ ci,
+                                                        const int32_t *__restrict__ level,
+                                                        const unsigned long long *__restrict__ fb,
+                                                        const int32_t *__restrict__ order, uint32_t count,
+                                                        int32_t lv1, double *sigma, double *coef, double *cent) {
+    static_assert(kBfsBlock / kWave == 4, "the LDS tree below adds four wave sums");
+    __shared__ double red[kBfsBlock / kWave];
+    const double *val = BACK ? coef : sigma;
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const int32_t v = order[i];
+        const int64_t b = rp[v], e = rp[v + 1];
+        double acc = 0.0;
+        for (int64_t k = b + threadIdx.x; k < e; k += 4 * kBfsBlock)
+            acc += bc_quad<BITS>(ci, level, fb, val, k, kBfsBlock, e, lv1);
+        acc = wave_sum(acc);
+        if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) bc_store<BACK>((red[0] + red[1]) + (red[2] + red[3]), v, sigma, coef, cent);
+        __syncthreads();
+    }
+}
+
+struct BcWork {
+    DBuf<double> sigma, coef, cent;
+    DBuf<int32_t> order_in, order_out;   // bucketed by the tiers of the in-rows / the out-rows
+    DBuf<unsigned long long> bits;       // level bitmap, all clear between launches
+    DBuf<uint32_t> cnt, off;
+    DBuf<int32_t> maxlevel;
+    std::vector<uint32_t> h_off_in, h_off_out;
+    int sh = kBcShort, lg = kBcLong;
+    uint32_t bits_rows = kBcBitsRows;
+};
+
+// order / h_off: the reached vertices of `level` by (level, tier of their row in rp); h_off has
+// 3 * (maxlevel + 1) + 1 entries.  Synchronises the stream (the offsets size the launches).
+int bc_buckets(gx_graph *g, const int32_t *level, const int64_t *rp, int32_t maxlevel, BcWork &b, int32_t *order,
+               std::vector<uint32_t> &h_off, hipStream_t s) {
+    const int64_t n = (int64_t)g->n;
+    const uint32_t nk = 3u * (uint32_t)(maxlevel + 1);
+    if (b.cnt.n < (size_t)nk + 1) {
+        GX_TRY(b.cnt.alloc(2 * (size_t)nk + 1));
+        GX_TRY(b.off.alloc(2 * (size_t)nk + 1));
+    }
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kBcTile - 1) / kBcTile, 1024);
+    GX_HIP_TRY(hipMemsetAsync(b.cnt.p, 0, (size_t)nk * 4, s));
+    hipLaunchKernelGGL(k_bc_bucket<false>, dim3(grid), dim3(kBfsBlock), 0, s, level, rp, n, maxlevel, b.sh, b.lg,
+                       b.cnt.p, order);
+    hipLaunchKernelGGL(k_bc_scan, dim3(1), dim3(kBfsBlock), 0, s, b.cnt.p, b.off.p, nk);
+    hipLaunchKernelGGL(k_bc_bucket<true>, dim3(grid), dim3(kBfsBlock), 0, s, level, rp, n, maxlevel, b.sh, b.lg,
+                       b.cnt.p, order);
+    GX_TRY(check_launch("k_bc_bucket"));
+    h_off.resize((size_t)nk + 1);
+    GX_HIP_TRY(hipMemcpyAsync(h_off.data(), b.off.p, ((size_t)nk + 1) * 4, hipMemcpyDeviceToHost, s));
+    GX_HIP_TRY(hipStreamSynchronize(s));
+    if (h_off[nk] > (uint64_t)n) return fail(GX_PANIC, "gx_betweenness: bucket offsets exceed n");
+    return GX_SUCCESS;
+}
+
+// The launches of level d's bucket, one per non-empty tier, probing level lv1.  A bucket of at
+// least bits_rows rows probes the bitmap of level lv1, set from that level's bucket (of order_in:
+// the same vertices in either order array) and cleared again; a smaller one reads level[x].
+template <bool BACK>
+void bc_level(const DevCSR &m, const int32_t *level, const int32_t *order, const std::vector<uint32_t> &h_off,
+              int32_t d, int32_t lv1, BcWork &b, hipStream_t s) {
+    const uint32_t *o = h_off.data() + 3 * (size_t)d;
+    const uint32_t *p = b.h_off_in.data() + 3 * (size_t)lv1;
+    const uint32_t probed = p[3] - p[0];
+    const bool bits = o[3] - o[0] >= b.bits_rows && probed > 0;
+    const unsigned long long *fb = b.bits.p;
+    auto mark = [&](int set) {
+        hipLaunchKernelGGL(k_bc_bits, dim3(grid_for(probed, kBfsBlock, 2048)), dim3(kBfsBlock), 0, s,
+                           b.order_in.p + p[0], probed, b.bits.p, set);
+    };
+    if (bits) mark(1);
+    if (const uint32_t c = o[1] - o[0]) {
+        const dim3 grid(grid_for(c, kBfsBlock, 8192));
+        if (bits)
+            hipLaunchKernelGGL((k_bc_rows<BACK, true>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[0], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+        else
+            hipLaunchKernelGGL((k_bc_rows<BACK, false>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[0], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+    }
+    if (const uint32_t c = o[2] - o[1]) {
+        const dim3 grid(grid_for((uint64_t)c * kWave, kBfsBlock, 8192));
+        if (bits)
+            hipLaunchKernelGGL((k_bc_wave<BACK, true>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[1], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+        else
+            hipLaunchKernelGGL((k_bc_wave<BACK, false>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[1], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+    }
+    if (const uint32_t c = o[3] - o[2]) {
+        const dim3 grid(std::min(c, 4096u));
+        if (bits)
+            hipLaunchKernelGGL((k_bc_block<BACK, true>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[2], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+        else
+            hipLaunchKernelGGL((k_bc_block<BACK, false>), grid, dim3(kBfsBlock), 0, s, m.rp.p, m.ci.p, level, fb,
+                               order + o[2], c, lv1, b.sigma.p, b.coef.p, b.cent.p);
+    }
+    if (bits) mark(0);
+}
+
+// Brandes' two passes over w's finished levels from src: sigma (left in b.sigma for the caller's
+// paths row) and the dependencies, added into b.cent.
+int bc_source(gx_graph *g, uint64_t src, BfsWork &w, BcWork &b, hipStream_t s) {
+    gx_ctx *ctx = g->ctx;
+    const int64_t n = (int64_t)g->n;
+    const DevCSR &in = g->directed ? g->AT : g->A;
+    int32_t maxlevel = 0;
+    {
+        KTimer kt(ctx, "bc_bucket", s);
+        GX_HIP_TRY(hipMemsetAsync(b.maxlevel.p, 0, 4, s));
+        hipLaunchKernelGGL(k_bc_depth, dim3(grid_for(n, kBfsBlock, 1024)), dim3(kBfsBlock), 0, s, w.level.p, n,
+                           b.maxlevel.p);
+        GX_TRY(check_launch("k_bc_depth"));
+        GX_HIP_TRY(hipMemcpyAsync(&maxlevel, b.maxlevel.p, 4, hipMemcpyDeviceToHost, s));
+        GX_HIP_TRY(hipStreamSynchronize(s));
+        if (maxlevel < 0 || maxlevel >= n) return fail(GX_PANIC, "gx_betweenness: level out of range");
+        GX_TRY(bc_buckets(g, w.level.p, in.rp.p, maxlevel, b, b.order_in.p, b.h_off_in, s));
+        if (g->directed) GX_TRY(bc_buckets(g, w.level.p, g->A.rp.p, maxlevel, b, b.order_out.p, b.h_off_out, s));
+    }
+    const int32_t *order_out = g->directed ? b.order_out.p : b.order_in.p;
+    const std::vector<uint32_t> &h_off_out = g->directed ? b.h_off_out : b.h_off_in;
+    GX_HIP_TRY(hipMemsetAsync(b.sigma.p, 0, (size_t)n * 8, s));
+    hipLaunchKernelGGL(k_bc_seed, dim3(1), dim3(1), 0, s, b.sigma.p, b.coef.p, (int32_t)src);
+    {
+        KTimer kt(ctx, "bc_sigma", s);
+        for (int32_t d = 1; d <= maxlevel; d++)
+            bc_level<false>(in, w.level.p, b.order_in.p, b.h_off_in, d, d - 1, b, s);
+    }
+    GX_TRY(check_launch("k_bc_rows (sigma)"));
+    {
+        KTimer kt(ctx, "bc_delta", s);
+        for (int32_t d = maxlevel - 1; d >= 1; d--)
+            bc_level<true>(g->A, w.level.p, order_out, h_off_out, d, d + 1, b, s);
+    }
+    return check_launch("k_bc_rows (delta)");
+}
+
 }  // namespace
 }  // namespace gx
 
@@ -880,6 +1256,48 @@ extern "C" int gx_bfs_parent(gx_graph *g, uint64_t src, int64_t *level_out, int6
     GX_TRY(device_end(g->ctx));
     if (level_out) GX_TRY(download(g->ctx, level_out, res_level, g->n, Xfer::Levels));
     GX_TRY(download(g->ctx, parent_out, res_parent, g->n, Xfer::Sign32));
+    return GX_SUCCESS;
+}
+
+extern "C" int gx_betweenness(gx_graph *g, const uint64_t *sources, uint64_t ns, double *centrality,
+                              double *paths) {
+    if (!g || !centrality || (ns > 0 && !sources)) return fail(GX_NULL_POINTER, "gx_betweenness: null argument");
+    for (uint64_t k = 0; k < ns; k++)
+        if (sources[k] >= g->n) return fail(GX_INVALID_INDEX, "gx_betweenness: source out of range");
+    gx_ctx *ctx = g->ctx;
+    GX_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const char *se = std::getenv("GX_BC_SHORT"), *le = std::getenv("GX_BC_LONG");
+    BcWork b;
+    b.sh = se ? std::max(0, std::atoi(se)) : kBcShort;
+    b.lg = std::max(b.sh, le ? std::atoi(le) : kBcLong);
+    // rows a bucket needs to probe a level bitmap: 0 always, -1 never
+    if (const char *be = std::getenv("GX_BC_BITS")) b.bits_rows = (uint32_t)std::atoll(be);
+    // the sigma pass reads in-edges whatever GX_BFS_TRANSPOSE says; built before the bracket
+    if (g->directed) GX_TRY(ensure_transpose(g));
+    GX_TRY(b.sigma.alloc(g->n));
+    GX_TRY(b.coef.alloc(g->n));
+    GX_TRY(b.bits.alloc(g->n / 64 + 1));
+    GX_TRY(b.cent.alloc(g->n));
+    GX_TRY(b.order_in.alloc(g->n));
+    if (g->directed) GX_TRY(b.order_out.alloc(g->n));
+    GX_TRY(b.maxlevel.alloc(1));
+    GX_TRY(device_begin(ctx));
+    GX_HIP_TRY(hipMemsetAsync(b.cent.p, 0, g->n * 8, s));
+    GX_HIP_TRY(hipMemsetAsync(b.bits.p, 0, (g->n / 64 + 1) * 8, s));
+    // g itself, never its hub-first copy: the copy permutes the rows, and with them the order
+    // of every sum, between a graph's first and second call
+    BfsWork w;
+    for (uint64_t k = 0; k < ns; k++) {
+        GX_TRY(bfs_levels(g, sources[k], w, [](bool, bool &queued) -> int {
+            queued = true;
+            return GX_SUCCESS;
+        }, false));
+        GX_TRY(bc_source(g, sources[k], w, b, s));
+        if (paths) GX_TRY(download(ctx, paths + k * g->n, b.sigma.p, g->n, Xfer::Raw64));
+    }
+    GX_TRY(device_end(ctx));
+    GX_TRY(download(ctx, centrality, b.cent.p, g->n, Xfer::Raw64));
     return GX_SUCCESS;
 }
 
