@@ -271,7 +271,7 @@ struct KTimer {
 // g is undirected and this is the algorithm's `calls`-th call with calls >= 2 (GX_HUB = 0 never,
 // 1 from the second call (default), 2 from the first).  *src is renamed into the copy's ids.
 int hub_for(gx_graph *g, int calls, gx_graph **out, uint64_t *src);
-// The results to download: on a copy (g->out_perm set) buf scattered through out_order into
+// The results to download: on a copy (g->out_perm set) buf gathered through out_perm into
 // the parent's vertex order (g->remap_tmp; elem = 4 or 8 bytes, n entries), else buf itself.
 // half = 1 (elem 4 only) lands in the second n 4-byte words of remap_tmp, so a call with two
 // 4-byte results keeps both there until they are downloaded.

@@ -317,23 +317,14 @@ __global__ __launch_bounds__(kWccBlock) void k_wcc_min_orig(const int32_t *__res
 
 // out[v] = the label of v's component, gathered through perm (x = perm[v], the hub-first
 // position of caller vertex v); vertices past `live` have no edges and are their own component.
-// Coalesced stores: the scatter below took 30 us per run on SYN-g500-22 (r05_wcc_kernel_stats.csv).
+// Coalesced stores: the scatter through order that it replaced took 30 us per run on
+// SYN-g500-22 (r05_wcc_kernel_stats.csv).
 __global__ void k_wcc_label_gather(const int32_t *__restrict__ parent, const int32_t *__restrict__ perm,
                                    const int32_t *__restrict__ minorig, int64_t n, int64_t live,
                                    int32_t *__restrict__ out) {
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
         const int32_t x = perm[v];
         out[v] = x < live ? minorig[parent[x]] : (int32_t)v;
-    }
-}
-
-// The same as a scatter through order (GX_REMAP=scatter): streaming reads, random stores.
-__global__ void k_wcc_label_orig(const int32_t *__restrict__ parent, const int32_t *__restrict__ order,
-                                 const int32_t *__restrict__ minorig, int64_t n, int64_t live,
-                                 int32_t *__restrict__ out) {
-    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t o = order[x];
-        out[o] = x < live ? minorig[parent[x]] : o;
     }
 }
 
@@ -424,14 +415,9 @@ extern "C" int gx_wcc(gx_graph *g, uint64_t *comp) {
             hipLaunchKernelGGL(k_wcc_min_orig, dim3(grid_for((uint64_t)live, kWccBlock, 2048)), dim3(kWccBlock), 0,
                                s, parent.p, g->out_order, live, giant_d, minorig);
         }
-        const char *re = std::getenv("GX_REMAP");
-        if (re && std::strcmp(re, "scatter") == 0)
-            hipLaunchKernelGGL(k_wcc_label_orig, dim3(vgrid), dim3(256), 0, s, parent.p, g->out_order, minorig, n,
-                               live, lab);
-        else
-            hipLaunchKernelGGL(k_wcc_label_gather, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, parent.p,
-                               g->out_perm, minorig, n, live, lab);
-        GX_TRY(check_launch("k_wcc_label_orig"));
+        hipLaunchKernelGGL(k_wcc_label_gather, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, parent.p, g->out_perm,
+                           minorig, n, live, lab);
+        GX_TRY(check_launch("k_wcc_label_gather"));
         res = lab;
     }
     GX_TRY(device_end(ctx));

@@ -203,11 +203,13 @@ def test_gpu_rmat_three_calls(ctx, directed):
 @pytest.mark.parametrize("env", [{"GX_BFS_ALPHA": "1", "GX_BFS_BETA": "1000"},
                                  {"GX_BFS_ALPHA": "1000", "GX_BFS_BETA": "1"},
                                  {"GX_HUB": "2"}, {"GX_HUB": "2", "GX_HUB_SORT": "0"},
-                                 {"GX_HUB": "2", "GX_REMAP": "scatter"}, {"GX_BFS_DEVICE": "0"},
-                                 {"GX_BFS_PARENT_PUSH": "1"}, {"GX_BFS_PARENT_PUSH": "1", "GX_HUB": "2"}])
+                                 {"GX_BFS_DEVICE": "0"},
+                                 {"GX_BFS_PARENT_PUSH": "1"}, {"GX_BFS_PARENT_PUSH": "1", "GX_HUB": "2"}],
+                         # env4 was the scatter remap, since removed: the others keep their ids
+                         ids=["env0", "env1", "env2", "env3", "env5", "env6", "env7"])
 def test_gpu_parents_do_not_depend_on_direction_or_copy(ctx, monkeypatch, env):
-    """Top-down or bottom-up levels, the hub-first copy (sorted rows or not, gathered or scattered
-    back), host-driven levels, and the push form of the parent pass where pull is the default."""
+    """Top-down or bottom-up levels, the hub-first copy (sorted rows or not), host-driven levels,
+    and the push form of the parent pass where pull is the default."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     for directed in (False, True):

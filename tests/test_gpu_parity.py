@@ -633,6 +633,18 @@ def test_wcc_sampling_modes(ctx, monkeypatch, env):
     np.testing.assert_array_equal(gpu_run(ctx, _G(csr, False), "WCC"), O.wcc(csr))
 
 
+def _odd_rmat(scale, ef, seed, n):
+    """The undirected R-MAT graph (scale, ef, seed) with its 2^scale vertices renamed to random
+    ids below n, n no multiple of 64: the last word of a BFS frontier bitmap is partial, and it
+    holds reachable vertices."""
+    from ldbc_graphalytics_platforms_graphblas_amd.graphio import csr_from_edges
+    csr = _rmat(scale, ef, seed).csr
+    u = np.repeat(np.arange(csr.n, dtype=np.int64), np.diff(csr.rowptr.astype(np.int64)))
+    v = csr.colidx.astype(np.int64)
+    ids = np.random.default_rng(11).permutation(n)[:csr.n]
+    return _G(csr_from_edges(n, ids[u[u < v]], ids[v[u < v]], None, symmetric=True), False)
+
+
 @pytest.mark.parametrize("device,nextbits,grid,qbits", [("1", "1", None, "1"), ("1", "1", None, "0"),
                                                         ("1", "0", None, "1"), ("1", "1", "3", "1"),
                                                         ("1", "0", "8192", "1"), ("0", "1", None, "1")])
@@ -645,7 +657,9 @@ def test_bfs_level_driver(ctx, monkeypatch, device, nextbits, grid, qbits, fused
     bitmap pass rebuilds it from the levels, and a top-down level after it builds its queue from
     that bitmap (GX_BFS_QBITS=1) or from the levels; GX_BFS_GRID caps the grid-stride kernels'
     grids (3 workgroups: many rounds per wave).  A level runs as two launches branching on the
-    plan's direction (GX_BFS_FUSED=1, the default) or as the four direction kernels."""
+    plan's direction (GX_BFS_FUSED=1, the default) or as the four direction kernels.  The two
+    graphs of 1 061 and 16 421 vertices go top-down, bottom-up twice and top-down again with
+    reachable vertices in the frontier bitmap's partial last word."""
     from ldbc_graphalytics_platforms_graphblas_amd.graphio import csr_from_edges
     monkeypatch.setenv("GX_BFS_DEVICE", device)
     monkeypatch.setenv("GX_BFS_FUSED", fused)
@@ -653,7 +667,8 @@ def test_bfs_level_driver(ctx, monkeypatch, device, nextbits, grid, qbits, fused
     monkeypatch.setenv("GX_BFS_QBITS", qbits)
     if grid:
         monkeypatch.setenv("GX_BFS_GRID", grid)
-    for g in (_rmat(14, 16, 4), _rmat(12, 8, 3, undirected=False)):
+    for g in (_rmat(14, 16, 4), _rmat(12, 8, 3, undirected=False), _odd_rmat(10, 8, 1, 1061),
+              _odd_rmat(14, 16, 4, 16421)):
         s = _src(g)
         np.testing.assert_array_equal(gpu_run(ctx, g, "BFS", source=s), O.bfs(g.csr, s))
     # a directed graph with its transpose (bottom-up levels): two calls on one graph
@@ -679,20 +694,21 @@ def test_bfs_direction_thresholds(ctx, monkeypatch, alpha, beta):
     and kept to the end, top-down almost throughout, and a mid setting; levels bit-exact."""
     monkeypatch.setenv("GX_BFS_ALPHA", alpha)
     monkeypatch.setenv("GX_BFS_BETA", beta)
-    for g in (_rmat(14, 16, 4), _rmat(12, 8, 3, undirected=False)):
+    for g in (_rmat(14, 16, 4), _rmat(12, 8, 3, undirected=False), _odd_rmat(10, 8, 1, 1061),
+              _odd_rmat(14, 16, 4, 16421)):
         s = _src(g)
         for _ in range(2):   # the second call runs on the hub-first copy / with the transpose
             np.testing.assert_array_equal(gpu_run(ctx, g, "BFS", source=s), O.bfs(g.csr, s))
 
 
 @pytest.mark.parametrize("env", [{"GX_HUB": "1"}, {"GX_HUB": "2"}, {"GX_HUB": "2", "GX_HUB_SORT": "0"},
-                                 {"GX_HUB": "2", "GX_WCC_ROUNDS": "2"}, {"GX_HUB": "2", "GX_REMAP": "scatter"}])
+                                 {"GX_HUB": "2", "GX_WCC_ROUNDS": "2"}])
 def test_hub_first_copy(ctx, monkeypatch, env):
     """BFS, WCC and SSSP on the hub-first relabelled copy of an undirected graph (built from
     the second call on a graph, GX_HUB=1, or from the first, GX_HUB=2; rows sorted by hub-first
     id, or in the parent's order with GX_HUB_SORT=0; WCC with one sampling round on the sorted
     copy, or two): results come back in the caller's vertex order -- levels and distances
-    gathered through the permutation (or scattered through its inverse, GX_REMAP=scatter), WCC labels renamed to each component's smallest caller
+    gathered through the permutation, WCC labels renamed to each component's smallest caller
     id -- on graphs with many components, isolated vertices and unreachable ones, over three
     calls on one graph."""
     from ldbc_graphalytics_platforms_graphblas_amd import algorithms as A
