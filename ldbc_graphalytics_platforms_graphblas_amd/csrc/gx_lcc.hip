@@ -151,6 +151,7 @@ constexpr int kClassTile = 4096;
 
 __global__ __launch_bounds__(kLccBlock) void k_lcc_items(const int64_t *__restrict__ orp,
                                                          const int64_t *__restrict__ irp, int64_t v0, int64_t v1,
+                                                         int32_t wave_max, int32_t wave2_max, int32_t block_max,
                                                          uint64_t *items0, uint64_t *items1, uint64_t *items2,
                                                          int32_t *big_list, uint32_t *counts /* 4 tiers + max d */) {
     constexpr int kTiers = 4;
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(kLccBlock) void k_lcc_items(const int64_t *__restri
             for (int64_t u = t0 + threadIdx.x; u < t1; u += kLccBlock) {
                 const int64_t d = orp[u + 1] - orp[u], e = irp[u + 1] - irp[u];
                 if (d == 0 || e == 0) continue;
-                const int tier = d <= kWaveMax ? 0 : (d <= kWave2Max ? 1 : (d <= kBlockMax ? 2 : 3));
+                const int tier = d <= wave_max ? 0 : (d <= wave2_max ? 1 : (d <= block_max ? 2 : 3));
                 const int64_t group = tier == 2 ? kBlockGroup : kWaveGroup;
                 const uint32_t ni = tier == 3 ? 1u : (uint32_t)((e + group - 1) / group);
                 if (pass == 0) {
@@ -677,9 +678,22 @@ struct LccItems {
     uint32_t hc[5] = {0, 0, 0, 0, 0};   // items per tier, then the largest workgroup-tier |O(u)|
 };
 
+// A tier limit from the environment: GX_LCC_WAVE_MAX / GX_LCC_WAVE2_MAX / GX_LCC_BLOCK_MAX can
+// only lower kWaveMax / kWave2Max / kBlockMax (clamped to [1, the compile-time value]), so the
+// static wave tables and the kBlockSlots cap hold whatever is set.  Tests use them to reach the
+// workgroup tier and the merge fallback on small graphs.
+int32_t lcc_tier_limit(const char *name, int32_t compiled) {
+    const char *e = std::getenv(name);
+    if (!e || !*e) return compiled;
+    return (int32_t)std::min<long>(std::max<long>(std::atol(e), 1), compiled);
+}
+
 int lcc_items(const LccOrient &O, int64_t v0, int64_t v1, LccItems &L, hipStream_t s) {
     const int64_t nv = v1 - v0;
     if (nv <= 0 || O.m == 0) return GX_SUCCESS;
+    const int32_t wave_max = lcc_tier_limit("GX_LCC_WAVE_MAX", kWaveMax);
+    const int32_t wave2_max = std::max(wave_max, lcc_tier_limit("GX_LCC_WAVE2_MAX", kWave2Max));
+    const int32_t block_max = std::max(wave2_max, lcc_tier_limit("GX_LCC_BLOCK_MAX", kBlockMax));
     const uint64_t icap = (uint64_t)nv + (uint64_t)O.m / kWaveGroup + 64;
     DBuf<uint32_t> counts;
     GX_TRY(L.items0.alloc(icap));
@@ -689,8 +703,8 @@ int lcc_items(const LccOrient &O, int64_t v0, int64_t v1, LccItems &L, hipStream
     GX_TRY(counts.alloc(5));
     GX_HIP_TRY(hipMemsetAsync(counts.p, 0, 20, s));
     hipLaunchKernelGGL(k_lcc_items, dim3((unsigned)std::min<int64_t>((nv + kClassTile - 1) / kClassTile, 2048)),
-                       dim3(kLccBlock), 0, s, O.orp.p, O.irp.p, v0, v1, L.items0.p, L.items1.p, L.items2.p, L.big.p,
-                       counts.p);
+                       dim3(kLccBlock), 0, s, O.orp.p, O.irp.p, v0, v1, wave_max, wave2_max, block_max, L.items0.p,
+                       L.items1.p, L.items2.p, L.big.p, counts.p);
     GX_TRY(check_launch("k_lcc_items"));
     GX_HIP_TRY(hipMemcpyAsync(L.hc, counts.p, 20, hipMemcpyDeviceToHost, s));
     GX_HIP_TRY(hipStreamSynchronize(s));
@@ -711,13 +725,18 @@ int lcc_count_items(gx_graph *g, const LccOrient &O, const LccItems &L, unsigned
     const uint64_t *items0 = L.items0.p, *items1 = L.items1.p, *items2 = L.items2.p;
     {
         KTimer kt(ctx, "lcc_triangles", s);
-        if (hc[0])
+        // one nested timer per launched tier: their launch counts tell which tiers ran
+        if (hc[0]) {
+            KTimer kw(ctx, "lcc_wave", s);
             hipLaunchKernelGGL(k_lcc_wave<512>, dim3(grid_for((uint64_t)hc[0] * kWave, kLccBlock, 8192)),
                                dim3(kLccBlock), 0, s, O.orp.p, O.ocode.p, O.irp.p, O.icode.p, items0, hc[0], tc);
+        }
         GX_TRY(check_launch("k_lcc_wave<512>"));
-        if (hc[1])
+        if (hc[1]) {
+            KTimer kw(ctx, "lcc_wave2", s);
             hipLaunchKernelGGL(k_lcc_wave<1024>, dim3(grid_for((uint64_t)hc[1] * kWave, kLccBlock, 8192)),
                                dim3(kLccBlock), 0, s, O.orp.p, O.ocode.p, O.irp.p, O.icode.p, items1, hc[1], tc);
+        }
         GX_TRY(check_launch("k_lcc_wave<1024>"));
         if (hc[2]) {
             const uint32_t slots = std::max<uint32_t>(64, std::min<uint32_t>(kBlockSlots, [&] {
@@ -728,12 +747,14 @@ int lcc_count_items(gx_graph *g, const LccOrient &O, const LccItems &L, unsigned
             if (slots * 8 > 65536)
                 GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lcc_block),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(slots * 8)));
+            KTimer kb(ctx, "lcc_block", s);
             hipLaunchKernelGGL(k_lcc_block, dim3(std::min<uint32_t>(hc[2], 4096)), dim3(kLccBlock),
                                (size_t)slots * 8, s, O.orp.p, O.ocode.p, O.irp.p, O.icode.p, items2, hc[2], slots,
                                tc);
         }
         GX_TRY(check_launch("k_lcc_block"));
         if (hc[3]) {
+            KTimer km(ctx, "lcc_merge", s);
             for (int32_t u : L.h_big) {
                 hipLaunchKernelGGL(k_lcc_merge_in, dim3(64), dim3(kLccBlock), 0, s, O.orp.p, O.ocode.p, O.irp.p,
                                    O.icode.p, u, tc);
