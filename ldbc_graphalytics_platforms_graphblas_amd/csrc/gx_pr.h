@@ -190,6 +190,12 @@ struct PrPart {
     DBuf<double> fdpart;
     DBuf<uint32_t> fdticket;
     uint32_t ndblocks = 0;
+    // isolated rows in closed form (GX_PR_ISO_CLOSED, pr_plan_sorted): the last iso_units units are
+    // blocks without entries whose rows all lie past `live` (score teleport, x never gathered).
+    // They hold the last iso_dblocks dangling slots, and every launch but a run's last leaves
+    // them out and adds iso_rows * teleport to the dangling sum instead
+    uint32_t iso_units = 0, iso_dblocks = 0;
+    uint64_t iso_rows = 0;
     int kernel = 2;              // 1 = k_pr_pull (CSR-Adaptive, GX_PR_KERNEL=adaptive), 2 = k_pr_pull_units
     // where the sorted plan reads its entries: local row i is row order[i] of (src_rp, src_ci)
     // with every column c renamed perm[c] (gx_pagerank's hub-first plan), or row i itself with

@@ -21,7 +21,10 @@
 // A block's column-sorted entries are then recoded from the front: its pair prefix as 4-byte
 // slots of two entries of one 16-byte pair of x (ppk / pbase, gather_pairs: one 16-B x load per
 // two entries), the dense columns after it as 2-byte narrow codes (npk / nbase, gather_narrow);
-// spk / gbase / sci serve the wide remainder (gather_units).
+// spk / gbase / sci serve the wide remainder (gather_units).  Before the recoding, the entries of
+// each column's (column pair's) run in the two prefixes are put in a bank-aware order
+// (k_bank_order): the run's 16 consecutive entries that one lane group of an LDS add covers
+// then hold rows of different bank slots where the run allows.
 // Gathered values are added into LDS row accumulators (ds_add_f64) in wave-arrival order:
 // scores agree with the row-order sum to ~1e-15 relative but are not bit-reproducible run to
 // run (the parity bar is 1e-12 relative, tests/test_gpu_parity.py).
@@ -44,6 +47,7 @@
 #include <cstring>
 
 #include "gx_pr.h"
+#include "gx_pr_bank.h"
 
 namespace gx {
 namespace {
@@ -84,6 +88,9 @@ struct SortedArgs {
     double *dpart;
     uint32_t *dticket;
     uint32_t ndblocks;
+    // isolated rows in closed form (GX_PR_ISO_CLOSED): rows of blocks left out of this launch, each
+    // of score teleport, added to the dangling sum by whoever writes it
+    double iso_rows;
     // split blocks
     const SortedUnit *units;
     uint32_t nunits;
@@ -149,7 +156,8 @@ __device__ __forceinline__ double epilogue_rows(const SortedArgs &a, int64_t r0,
 // ndblocks participants adds the partials up with the whole workgroup (thread t takes slots
 // t, t + kBS, ...; fixed tree, so the order is fixed) into the chunk's last x slot.
 template <int BS = kBS>
-__device__ __forceinline__ void dangling_publish(const SortedArgs &a, int32_t slot, double d, double *wred, int *last) {
+__device__ __forceinline__ void dangling_publish(const SortedArgs &a, int32_t slot, double d, double *wred, int *last,
+                                                 double teleport) {
     const int tid = threadIdx.x;
     d = wave_sum(d);
     __syncthreads();   // wred may still be read by an earlier reduction
@@ -179,7 +187,7 @@ __device__ __forceinline__ void dangling_publish(const SortedArgs &a, int32_t sl
 #pragma unroll
         for (int w = 0; w < BS / kWave; w++) all += wred[w];
         __hip_atomic_store(a.dticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.x_out[a.chunk - 1] = all;
+        a.x_out[a.chunk - 1] = all + a.iso_rows * teleport;
     }
 }
 
@@ -617,7 +625,8 @@ __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w,
             a.utimes[4 * w + 3] = (uint64_t)__builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_XCC_ID[3:0]
         }
     };
-    if (a.zero_slot && w == 0 && tid == 0) a.x_out[a.chunk - 1] = 0.0;
+    // no block publishes a dangling partial: item 0 writes the sum, 0 or the left-out rows' scores
+    if (a.zero_slot && w == 0 && tid == 0) a.x_out[a.chunk - 1] = a.iso_rows * teleport;
     if (w < a.nlong_pad) {
         if (w < a.nlong) long_segment(a, a.blocks[w], wred, teleport);
         stamp();
@@ -726,7 +735,7 @@ __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w,
         d = epilogue_rows(a, b.row_begin, nrows, acc, teleport);
     if (a.dslot) {
         const int32_t slot = a.dslot[u.blk];
-        if (slot >= 0) dangling_publish(a, slot, d, wred, &last);
+        if (slot >= 0) dangling_publish(a, slot, d, wred, &last, teleport);
     }
     stamp();
 }
@@ -774,7 +783,7 @@ __global__ __launch_bounds__(kCombBS) void k_pr_combine(SortedArgs a) {
     }
     double d = 0.0;
     if (tid < rows) d = sorted_epilogue(a, (int64_t)c.r0 + c.s0 + tid, s, teleport);
-    if (c.dslot >= 0) dangling_publish<kCombBS>(a, c.dslot, d, wred, &last);
+    if (c.dslot >= 0) dangling_publish<kCombBS>(a, c.dslot, d, wred, &last, teleport);
 }
 
 // The next work item for the whole workgroup, with no divergent branch anywhere: wave 0 takes
@@ -1021,6 +1030,124 @@ __global__ __launch_bounds__(256) void k_sorted_laneperm(const RowBlock *__restr
         const int64_t dst = z0 + (g << 6) + 4 * (rank >> 2) + (rank & 3);
         spk[dst] = p;
         sci[dst] = c;
+    }
+}
+
+// Bank-aware order inside column runs (GX_PR_BANK_ORDER; gx_pr_bank.h), for the pair prefix
+// (supergroups below qsplit[block]: runs of one column pair) and the narrow prefix (up to
+// nsplit[block]: runs of one column) of every sorted block, before their codes are emitted.  In
+// both layouts a 16-lane group of an LDS add covers 16 consecutive codes (slots), and a run has no
+// filler inside it, so consecutive entries of a run meet in a group.  Each piece of a run inside
+// a tile of kBankTile entries is dealt round-robin over its rows' classes (row mod 16), in place.
+// A piece keeps its entries (row and column move together), so the block's multiset of
+// (row, column), the runs' boundaries, hence every step, filler and junk half, are unchanged.
+// One 256-thread workgroup per tile, thread t holding entries 8 t .. 8 t + 7.  A long run is
+// dealt 2 Ki entries at a time, which leaves its classes' counts nearly even; dealt 64 at a time
+// (one wave per tile, ballots only) a class of random rows holds 4 +- 2 entries and the fullest
+// class sets the cycles of the piece's last groups: the model's conflict cycles x 0.79 against
+// x 0.63, 584 against 577 us per launch.  A piece's ends come from two scans over
+// the workgroup (the last head at or before an entry, the first after it); an entry's rank in
+// its class from an LDS counter of its piece and class (pieces of two or more entries start at
+// least 2 apart, so start / 2 names them; two 16-bit counters per word), in arrival order:
+// which of two rows of one class and run comes first is not fixed run to run, and does not
+// matter to the banks.  A tile may straddle the end of the pair prefix; a piece does not.  The
+// words of spk keep the column offset of the supergroup they came from, which neither prefix reads.
+constexpr int kBankTile = 2048, kBankBS = 256, kBankPer = kBankTile / kBankBS;
+__global__ __launch_bounds__(kBankBS) void k_bank_order(const RowBlock *__restrict__ blocks, const uint32_t *__restrict__ qsplit,
+                                                        const uint32_t *__restrict__ nsplit, uint32_t *spk, int32_t *sci) {
+    __shared__ uint32_t cnt2[kBankTile / 2][kBankClasses / 2];   // 32 KiB
+    __shared__ int32_t wred[2][kBankBS / kWave];
+    const RowBlock b = blocks[blockIdx.y];
+    const int64_t z0 = b.nz_begin, N = b.nz_end - z0;
+    const int64_t Nq = min(N, (int64_t)qsplit[blockIdx.y] << 8), Np = min(N, (int64_t)nsplit[blockIdx.y] << 8);
+    const int64_t ntiles = (Np + kBankTile - 1) / kBankTile;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    for (int64_t g = blockIdx.x; g < ntiles; g += gridDim.x) {
+        const int64_t t0 = g * kBankTile;
+        const int32_t nin = (int32_t)min<int64_t>(kBankTile, Np - t0);   // entries of the tile
+        uint32_t p[kBankPer], key[kBankPer];
+        int32_t c[kBankPer], s0[kBankPer], s1[kBankPer];
+        bool head[kBankPer];
+        for (int w = tid; w < kBankTile / 2 * (kBankClasses / 2); w += kBankBS) (&cnt2[0][0])[w] = 0u;
+        // the entry before the thread's first, for its head flag
+        const int32_t i0 = tid * kBankPer;
+        uint32_t prevkey = 0;
+        if (i0 > 0 && i0 < nin) {
+            const int64_t e = t0 + i0 - 1;
+            prevkey = e < Nq ? (uint32_t)sci[z0 + e] >> 1 : (uint32_t)sci[z0 + e];
+        }
+#pragma unroll
+        for (int j = 0; j < kBankPer; j++) {
+            const int32_t i = i0 + j;
+            const bool in = i < nin;
+            p[j] = in ? spk[z0 + t0 + i] : 0u;
+            c[j] = in ? sci[z0 + t0 + i] : 0;
+            key[j] = t0 + i < Nq ? (uint32_t)c[j] >> 1 : (uint32_t)c[j];
+        }
+        int32_t last = -1;
+#pragma unroll
+        for (int j = 0; j < kBankPer; j++) {
+            const int32_t i = i0 + j;
+            // the tile's first entry, the narrow prefix's first, an entry past the prefix, a new key
+            head[j] = i == 0 || i >= nin || t0 + i == Nq || key[j] != (j ? key[j - 1] : prevkey);
+            if (head[j]) last = i;
+            s0[j] = last;
+        }
+        int32_t first = kBankTile;
+#pragma unroll
+        for (int j = kBankPer - 1; j >= 0; j--) {
+            s1[j] = first;
+            if (head[j]) first = i0 + j;
+        }
+        // the last head of the threads before mine, the first head of the threads after mine
+        int32_t m0 = last, m1 = first;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int32_t v0 = __shfl_up(m0, d, kWave), v1 = __shfl_down(m1, d, kWave);
+            if (lane >= d) m0 = max(m0, v0);
+            if (lane + d < kWave) m1 = min(m1, v1);
+        }
+        if (lane == kWave - 1) wred[0][wave] = m0;
+        if (lane == 0) wred[1][wave] = m1;
+        int32_t before = __shfl_up(m0, 1, kWave), after = __shfl_down(m1, 1, kWave);
+        if (lane == 0) before = -1;
+        if (lane == kWave - 1) after = kBankTile;
+        __syncthreads();   // wred written, cnt2 zeroed
+        for (int w = 0; w < kBankBS / kWave; w++) {
+            if (w < wave) before = max(before, wred[0][w]);
+            if (w > wave) after = min(after, wred[1][w]);
+        }
+        uint32_t rank[kBankPer];
+#pragma unroll
+        for (int j = 0; j < kBankPer; j++) {
+            if (s0[j] < 0) s0[j] = before;   // entry 0 of the tile is a head, so before >= 0 here
+            s1[j] = min(s1[j], after);
+            rank[j] = 0;
+            if (s1[j] - s0[j] > 1) {
+                const uint32_t cls = p[j] & (uint32_t)(kBankClasses - 1);
+                const uint32_t old = atomicAdd(&cnt2[s0[j] >> 1][cls >> 1], 1u << (16 * (cls & 1)));
+                rank[j] = (old >> (16 * (cls & 1))) & 0xffffu;
+            }
+        }
+        __syncthreads();   // every entry counted, and every load of the tile done
+#pragma unroll
+        for (int j = 0; j < kBankPer; j++) {
+            const uint32_t n = (uint32_t)(s1[j] - s0[j]);
+            if (n <= 1) continue;
+            uint32_t cnt[kBankClasses];
+#pragma unroll
+            for (int k = 0; k < kBankClasses / 2; k++) {
+                const uint32_t w = cnt2[s0[j] >> 1][k];
+                cnt[2 * k] = w & 0xffffu;
+                cnt[2 * k + 1] = w >> 16;
+            }
+            const uint32_t k = bank_deal_pos(cnt, p[j] & (uint32_t)(kBankClasses - 1), rank[j]);
+            const bool pairs = t0 + s0[j] < Nq;
+            const int64_t dst = z0 + t0 + s0[j] + (pairs ? bank_pair_pos(k, n) : k);
+            spk[dst] = p[j];
+            if (pairs) sci[dst] = c[j];   // a narrow run is one column
+        }
+        __syncthreads();   // cnt2 and wred are rewritten by the next tile
     }
 }
 
@@ -1756,6 +1883,16 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
                 prun += ((uint64_t)h_pcount[i] + kPSg - 1) / kPSg * kPSg;
                 p->npair += (uint64_t)Ep;
             }
+            // the order inside the runs of both prefixes, now that they are known, before their codes
+            // (GX_PR_BANK_ORDER=0: ascending rows, as the stable sort leaves them).  On where the pair
+            // slots are on by default, the huge graph's single plan
+            if (env_int("GX_PR_BANK_ORDER", huge && !piece ? 1 : 0, 0, 1) == 1) {
+                clk.mark("prefix splits");
+                hipLaunchKernelGGL(k_bank_order, dim3(64, nsb), dim3(kBankBS), 0, s, d_sort, d_psplit.p, d_nsplit.p, p->spk.p,
+                                   p->sci.p);
+                GX_TRY(check_launch("k_bank_order"));
+                clk.mark("bank order");
+            }
             // the pair slots: padding everywhere, then each block's prefix
             p->pnull_sg = (uint32_t)(prun / kPSg);
             p->npslots = prun + kPSg;
@@ -1836,6 +1973,27 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     // GX_PR_COMBINE=1: the multi-unit blocks combined by k_pr_combine (stripes), not by their
     // last arriving unit
     p->comb_kernel = env_int("GX_PR_COMBINE", piece ? 1 : 0, 0, 1) == 1;
+    // Isolated rows in closed form (GX_PR_ISO_CLOSED=0: off), with the fused dangling sum only.  A
+    // block without entries whose rows all have out-degree 0 holds vertices without any edge: their
+    // score is teleport, nobody gathers their x (a column of the pull matrix is a vertex with
+    // out-edges), and their dangling mass is rows * teleport.  Such rows are known without a look
+    // at every out-degree where they lie past `live` (a partition's xd rows) or inside the plan's
+    // one range of dangling rows (the hub-first single plan, whose rows all sit in the chunk:
+    // their x then keeps the value of the run's start, which nothing reads).  An empty block of
+    // a directed graph may hold rows with out-edges only: they still need x' = r / (outdeg / d)
+    // and stay as they are.  SYN-8_5: 172 of 521 blocks, each 16 320 out-degree loads, as many
+    // stores and a dangling partial per launch.  These blocks' units go last and their slots are
+    // the last; every launch but a run's last leaves them out (pr_step_sorted).
+    bool long_dangling = false;
+    for (const RowBlock &b : longb) long_dangling |= h_outdeg[b.row_begin] == 0;
+    const bool iso_on = env_int("GX_PR_ISO_CLOSED", 1, 0, 1) == 1 && p->nd > 0 && !long_dangling;
+    auto iso_block = [&](const RowBlock &b) {
+        if (!iso_on || b.nz_begin != b.nz_end || b.row_end <= b.row_begin) return false;
+        if ((uint64_t)b.row_begin >= p->live) return true;
+        return p->d_range && b.row_begin >= p->d0 && b.row_end <= p->d0 + (int64_t)p->nd;
+    };
+    p->iso_units = p->iso_dblocks = 0;
+    p->iso_rows = 0;
     std::vector<CombStripe> stripes;
     std::vector<char> multi(longb.size() + sortb.size(), 0);
     if (sortb.empty()) GX_HIP_TRY(hipStreamSynchronize(s));   // the temporaries above
@@ -1975,8 +2133,22 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             (void)E;
             return (eff_entries(u.blk - (int32_t)longb.size()) + u.nunits - 1) / u.nunits + rowc * R;
         };
-        std::stable_sort(units.begin(), units.end(),
-                         [&](const SortedUnit &x, const SortedUnit &y) { return cost(x) > cost(y); });
+        auto iso_unit = [&](const SortedUnit &u) { return iso_block(sortb[u.blk - longb.size()]); };
+        std::stable_sort(units.begin(), units.end(), [&](const SortedUnit &x, const SortedUnit &y) {
+            const bool ix = iso_unit(x), iy = iso_unit(y);
+            if (ix != iy) return iy;   // the closed-form blocks last, whatever their cost
+            return cost(x) > cost(y);
+        });
+        for (const SortedUnit &u : units)
+            if (iso_unit(u)) {
+                p->iso_units++;
+                p->iso_rows += (uint64_t)(u.r1 - u.r0);
+            }
+        // something has to run to write the sum: a graph of isolated rows alone keeps its items
+        if (p->nlong_pad + (uint32_t)units.size() == p->iso_units) {
+            p->iso_units = 0;
+            p->iso_rows = 0;
+        }
         // (Smallest first, or largest and smallest alternating, ran 88 and 120 us against 72 on
         // SYN-7_5 and 1133 against 753 on SYN-8_5: a block's interleaved units must run
         // together, tools/r03_order_ab.sh.)
@@ -2020,8 +2192,6 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     // per block holding dangling rows
     {
         std::vector<int32_t> slot(all.size(), -1);
-        bool long_dangling = false;
-        for (const RowBlock &b : longb) long_dangling |= h_outdeg[b.row_begin] == 0;
         uint32_t nd = 0;
         auto dangling_in = [&](int64_t r0, int64_t r1) {
             if (p->d_range)   // the dangling rows are [d0, d0 + nd)
@@ -2032,12 +2202,22 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
         };
         for (size_t i = longb.size(); i < all.size(); i++) {
             if (p->comb_kernel && multi[i]) continue;   // its stripes publish instead
+            if (p->iso_units && iso_block(all[i])) continue;   // the last slots, below
             if (dangling_in(all[i].row_begin, all[i].row_end)) slot[i] = (int32_t)nd++;
         }
         for (CombStripe &c : stripes)
             if (dangling_in((int64_t)c.r0 + c.s0, (int64_t)c.r0 + c.s1)) c.dslot = (int32_t)nd++;
+        // the closed-form blocks' slots last: a launch without them sums the slots before
+        for (size_t i = longb.size(); i < all.size() && p->iso_units; i++)
+            if (iso_block(all[i])) {
+                slot[i] = (int32_t)nd++;
+                p->iso_dblocks++;
+            }
         p->fused_dangling = p->nd > 0 && nd > 0 && !long_dangling;
         p->ndblocks = nd;
+        if (env_int("GX_PR_VERBOSE", 0, 0, 3))
+            std::fprintf(stderr, "[gx_pr] closed-form isolated rows: %u of %u units, %llu rows, %u of %u dangling slots\n",
+                         p->iso_units, p->nunits, (unsigned long long)p->iso_rows, p->iso_dblocks, nd);
         if (p->fused_dangling) {
             GX_TRY(p->dslot.alloc(std::max<size_t>(all.size(), 1)));
             GX_TRY(p->fdpart.alloc(nd));
@@ -2104,10 +2284,21 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
     if (p->npair && (reinterpret_cast<uintptr_t>(x_full) & 15))
         return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots need x 16-byte aligned");
     a.queue = p->queue.p;
+    // Isolated rows in closed form: a launch whose scores nobody asks for leaves the closed-form
+    // blocks (the last iso_units items, the last iso_dblocks dangling slots) out and has the
+    // dangling sum's writer add their rows * teleport: the last of the remaining publishers, or
+    // item 0 when none is left.  The run's last launch writes their scores and keeps every item.
+    a.iso_rows = 0.0;
+    if (!rank_out && p->fused_dangling && p->iso_units) {
+        a.nunits -= p->iso_units;
+        a.ndblocks -= p->iso_dblocks;
+        a.iso_rows = (double)p->iso_rows;
+        if (a.ndblocks == 0) a.zero_slot = 1;
+    }
     const char *times_path = std::getenv("GX_PR_UNIT_TIMES");   // debug: not under graph capture
-    const uint32_t nw = p->nlong_pad + p->nunits;
+    const uint32_t nw = p->nlong_pad + a.nunits;
     if (times_path && nw) {
-        if (!p->utimes.p) GX_TRY(p->utimes.alloc(4 * (size_t)nw));
+        if (!p->utimes.p) GX_TRY(p->utimes.alloc(4 * (size_t)(p->nlong_pad + p->nunits)));
         a.utimes = p->utimes.p;
     }
     if (nw) {
@@ -2117,7 +2308,9 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
         // One workgroup per CU also keeps fewer concurrent sweeps of x: SYN-7_5 ran 100-104 us per
         // launch against 109-125 with two (round 2, tools/pr_units_sweep.sh).
         const size_t lds = (size_t)(1 << kRowBits) * sizeof(double);
-        const bool use_queue = p->queue_on == 1 || (p->queue_on == -1 && nw >= 2u * (unsigned)std::max(1, p->ctx->num_cus));
+        // (by the plan's items, so that every launch of a run takes the same kernel)
+        const bool use_queue = p->queue_on == 1 || (p->queue_on == -1 && p->nlong_pad + p->nunits >=
+                                                                              2u * (unsigned)std::max(1, p->ctx->num_cus));
         const unsigned nq = std::min<unsigned>(nw, (unsigned)std::max(1, p->ctx->num_cus));
         // (narrow gathers three rounds deep ran the same: SYN-8_5 752-753 against 753-754
         // us, SYN-7_5 72.1-73.2 against 71.5-72.4; tools/r03_depth_ab.sh)
