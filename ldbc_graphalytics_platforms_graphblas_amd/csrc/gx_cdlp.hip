@@ -2370,7 +2370,20 @@ extern "C" int gx_cdlp(gx_graph *g, int iters, uint64_t *labels) {
         GX_HIP_TRY(hipMemsetAsync(C->rcnt.p, 0, sizeof(unsigned int) * iters, s));
     }
     // the recount bound (GX_CDLP_BOUND=0: off): an active iteration skips the vertices whose
-    // label provably keeps a strict majority
+    // label provably keeps a strict majority.
+    // vlb / vchg / hvalid live in the cache and are zeroed only when allocated: a call starts with
+    // the last call's values in them.  That is safe because of two things, which must stay true
+    // together: (1) the bound is read only by sparse iterations (bound_keeps tests a.sparse), and
+    // those start at it >= 2 (`active && it >= 2` below; k_cdlp_mark writes hvalid before them);
+    // (2) iteration it = 1 is a full one (act = nullptr), in which every tier kernel calls
+    // bound_set for every vertex of degree > 0 -- iteration 0's shortcuts (k_cdlp_first_sorted /
+    // k_cdlp_first_dir) write neither array.  A vertex of degree 0 is never active.  If active
+    // iterations ever start before it = 2, or a tier stops calling bound_set, clear vchg and
+    // hvalid here instead.  tests/test_call_history.py sequence (c) guards the histories: calls of
+    // 0 to 40 iterations mixed on one graph (short after long, after an early exit, the cache
+    // dropped in between), every result against the oracle.  It is not known to catch an edit
+    // that breaks (2): a trial build whose iteration 1 skipped bound_set still passed it (any
+    // dense iteration sets every bound anew, which may be what hides the stale values).
     CdlpBound bound{nullptr, nullptr, nullptr};
     if (env_on("GX_CDLP_BOUND")) {
         if (C->vlb.n < (size_t)n) {

@@ -1038,6 +1038,7 @@ struct SsspWork {
     hipGraphExec_t gexec = nullptr;
     hipStream_t g_stream = nullptr;
     unsigned g_grid = 0;
+    SsspBufs g_bufs{};             // the kernel argument the graph was captured with
     ~SsspWork() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -1071,8 +1072,18 @@ struct SsspWork {
         }
         return check_launch("k_sssp_relax");
     }
+    // The captured kernels hold B by value: every member, pointer or scalar (delta, dense_div,
+    // ...), is part of the capture's key.  Compared member by member (the struct has padding).
+    static bool same_bufs(const SsspBufs &a, const SsspBufs &b) {
+        return a.rp == b.rp && a.lend == b.lend && a.ci == b.ci && a.w == b.w && a.dist == b.dist &&
+               a.relaxed == b.relaxed && a.nsw == b.nsw && a.bstamp == b.bstamp && a.ostamp == b.ostamp &&
+               a.sbits == b.sbits && a.nbits == b.nbits && a.q[0] == b.q[0] && a.q[1] == b.q[1] && a.ring == b.ring &&
+               a.ovf[0] == b.ovf[0] && a.ovf[1] == b.ovf[1] && a.settled == b.settled && a.ring_cap == b.ring_cap &&
+               a.delta == b.delta && a.inv_delta == b.inv_delta && a.st == b.st && a.stats == b.stats &&
+               a.dense_div == b.dense_div;
+    }
     int capture(const SsspBufs &B, unsigned grid, hipStream_t s) {
-        if (gexec && g_stream == s && g_grid == grid) return GX_SUCCESS;
+        if (gexec && g_stream == s && g_grid == grid && same_bufs(g_bufs, B)) return GX_SUCCESS;
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
         gexec = nullptr;
@@ -1090,6 +1101,7 @@ struct SsspWork {
         GX_HIP_TRY(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
         g_stream = s;
         g_grid = grid;
+        g_bufs = B;
         return GX_SUCCESS;
     }
 };
