@@ -65,7 +65,8 @@ struct RowBlock {
 // nsg: the block's first code in PrPart::npk and its 512-code supergroups); [lo, hi) is the
 // wide 4-byte remainder.  Unit j of k takes narrow rounds j, j + k, ... as well.
 // Before the narrow codes, the block's pair prefix (pbeg, psg: its first slot in PrPart::ppk and
-// its 256-slot supergroups), in rounds dealt to the units the same way.
+// its 256-slot supergroups), in rounds dealt to the units the same way, and before those the
+// block's run region (rbeg, rsg: its first code in PrPart::rpk and its 512-code supergroups).
 struct SortedUnit {
     int64_t lo;
     int64_t hi;
@@ -82,7 +83,8 @@ struct SortedUnit {
     int32_t r0, r1;     //   supergroup seg
     int64_t pbeg;       // first pair slot of the block (a multiple of 256)
     int32_t psg;        // pair supergroups (256 slots each) of the block
-    int32_t pad;
+    int32_t rsg;        // run supergroups (512 codes each) of the block, ahead of the pair prefix
+    int64_t rbeg;       // first run code of the block in PrPart::rpk (a multiple of 512)
 };
 
 // A row stripe of a multi-unit block, combined by k_pr_combine after the units' launch
@@ -158,6 +160,15 @@ struct PrPart {
     uint64_t npfill = 0;         // filler halves of the slots (odd column pairs, steps above 3)
     uint64_t npslots = 0;        // slots, fillers and padding included
     uint32_t pnull_sg = 0;       // an all-padding pair supergroup (the pair of x's zero slot)
+    // run groups (gx_pr_sorted.hip gather_runs, gx_pr_runs.h): 64 two-byte codes (sel << 14 | row)
+    // of one column pair, 8 groups per 512-code supergroup, per block a 512-aligned run ahead of
+    // its pair prefix
+    DBuf<uint16_t> rpk;
+    DBuf<uint32_t> rpair;        // per run group: its column pair (8 per supergroup)
+    uint64_t nrun = 0;           // entries held in run codes
+    uint64_t nrpad = 0;          // padding codes that round the runs up to whole groups
+    uint64_t nrcodes = 0;        // run codes, padding and the null supergroup included
+    uint32_t rnull_sg = 0;       // an all-padding run supergroup (the pair of x's zero slot)
     int sorted_nnz = 65536;      // entries per block
     int sorted_rows = 4096;      // rows per block (LDS accumulators)
     int64_t unit_nnz = 0;        // target entries per unit

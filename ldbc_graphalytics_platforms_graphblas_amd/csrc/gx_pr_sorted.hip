@@ -18,11 +18,13 @@
 // entry, like the CSR column index.  Inside every full 64-entry group the entries are then
 // permuted (k_sorted_laneperm) so that each LDS-add instruction hits distinct banks; the
 // group's column set, hence its gathers' lines, is unchanged.
-// A block's column-sorted entries are then recoded from the front: its pair prefix as 4-byte
+// A block's column-sorted entries are then recoded from the front: its run region as 2-byte
+// codes in groups of 64 of one 16-byte pair of x (rpk / rpair, gather_runs: one x load per wave
+// and 8 groups, gx_pr_runs.h), its pair prefix as 4-byte
 // slots of two entries of one 16-byte pair of x (ppk / pbase, gather_pairs: one 16-B x load per
 // two entries), the dense columns after it as 2-byte narrow codes (npk / nbase, gather_narrow);
 // spk / gbase / sci serve the wide remainder (gather_units).  Before the recoding, the entries of
-// each column's (column pair's) run in the two prefixes are put in a bank-aware order
+// each column's (column pair's) run in the three prefixes are put in a bank-aware order
 // (k_bank_order): the run's 16 consecutive entries that one lane group of an LDS add covers
 // then hold rows of different bank slots where the run allows.
 // Gathered values are added into LDS row accumulators (ds_add_f64) in wave-arrival order:
@@ -48,6 +50,7 @@
 
 #include "gx_pr.h"
 #include "gx_pr_bank.h"
+#include "gx_pr_runs.h"
 
 namespace gx {
 namespace {
@@ -59,6 +62,8 @@ constexpr int kU = 8;            // entries per lane and round (two 16-B index l
 constexpr int kRound = kBS * kU; // entries of one round of a workgroup
 constexpr int kNSg = 512;        // codes of a narrow supergroup: one wave's 16-B load per lane
 constexpr int kPSg = 256;        // slots of a pair supergroup: one wave's 16-B load per lane
+constexpr int kRunFillCost = 32;  // GX_PR_RUN_FILL_COST: quarters of an entry per padding code
+constexpr int kRunCost = 2;       // GX_PR_RUN_COST: quarters of a narrow entry's cost per run code
 constexpr int kJunkRow = (1 << kRowBits) - kWave;   // accumulators [16320, 16384) absorb fillers
 constexpr int kMaxBlockRows = kJunkRow;             // rows of a sorted block
 static_assert(kMaxBlockRows == kPlanBlockRows, "gx_pr.h block rows");
@@ -104,6 +109,9 @@ struct SortedArgs {
     const uint32_t *ppk;     // pair slots
     const uint32_t *pbase;   // per pair supergroup: the pair index before its first slot
     uint32_t pnull_sg;       // all-padding pair supergroup (base = the pair of zero_col)
+    const uint16_t *rpk;     // run codes
+    const uint32_t *rpair;   // per run group: its column pair (8 per run supergroup)
+    uint32_t rnull_sg;       // all-padding run supergroup (every group the pair of zero_col)
     double *xd;              // x of the rows past `live` (store_x, gx_pr.h)
     int64_t live;
     // work queue (GX_PR_QUEUE): [0] next work item, [1] workgroups done (reset by the last)
@@ -605,6 +613,96 @@ __device__ __forceinline__ void gather_pairs(const SortedArgs &a, const SortedUn
     }
 }
 
+// The run region of a block, ahead of its pair prefix (gx_pr_runs.h): 2-byte codes sel << 14 | row
+// in groups of 64 codes of one column pair (columns 2p and 2p + 1; sel = the column's low bit).  A
+// pair's run starts on a group and its last group ends in padding codes (sel 0, the lane's junk
+// row).  A run supergroup of 512 codes is one wave-load of 16 B per lane (lane l: codes l + 64 k,
+// stored lane-major, so instruction k is group k) and has a header of 8 pair indices, rpair.  The
+// wave gets the 8 pairs of x by one 16-B load per lane (lane l: the pair of group l mod 8) and reads
+// group k's two values back from lane k (v_readlane): no per-lane gather and no scan.  The header
+// and x come by vector loads: a scalar load's wait (lgkmcnt) would also wait for the LDS adds in
+// flight.  Rounds, null supergroup and pipeline as in gather_narrow.  x_in must be 16-byte aligned
+// and the chunk even (pr_plan_sorted, pr_step_sorted).
+template <int CP>
+__device__ __forceinline__ void gather_runs(const SortedArgs &a, const SortedUnit &u, double *acc) {
+    constexpr int W = kBS / kWave;   // supergroups per round
+    const int32_t nrounds = (u.rsg + W - 1) / W;
+    if (u.unit >= nrounds) return;
+    const int32_t nr = (nrounds - u.unit + u.nunits - 1) / u.nunits;
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = tid >> 6;
+    const uint32_t sg0 = (uint32_t)(u.rbeg / kRunSg);
+    const char *xb = reinterpret_cast<const char *>(a.x_in);
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 16-B aligned (512-code runs)
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    struct Rd {
+        u32x4 q;
+        uint32_t pair;   // lane l: the pair of group l mod 8
+    };
+    struct Gt {
+        d2 g;            // lane l: x of the pair of group l mod 8
+        uint32_t c[4];   // the lane's 8 codes, decoded by the adds
+    };
+    auto load = [&](Rd &d, int32_t i) {
+        const int32_t sg = (u.unit + i * u.nunits) * W + wave;
+        const uint32_t g = sg < u.rsg ? sg0 + (uint32_t)sg : a.rnull_sg;
+        const u32x4 *qa = reinterpret_cast<const u32x4 *>(a.rpk + (size_t)g * kRunSg) + lane;
+        d.q = (CP & 1) ? __builtin_nontemporal_load(qa) : *qa;
+        d.pair = a.rpair[(size_t)g * kRunSgGroups + (lane & (kRunSgGroups - 1))];
+    };
+    // the hub lines: default cache policy
+    auto issue = [&](const Rd &d, Gt &t) {
+        const uint32_t w[4] = {d.q.x, d.q.y, d.q.z, d.q.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            t.c[k] = w[k];
+            asm volatile("" : "+v"(t.c[k]));
+        }
+        t.g = *reinterpret_cast<const d2 *>(xb + (d.pair << 4));
+    };
+    auto add = [&](const Gt &t) {
+        const int xl = __double2loint(t.g.x), xh = __double2hiint(t.g.x);
+        const int yl = __double2loint(t.g.y), yh = __double2hiint(t.g.y);
+#pragma unroll
+        for (int k = 0; k < kRunSgGroups; k++) {
+            const double xk = __hiloint2double(__builtin_amdgcn_readlane(xh, k), __builtin_amdgcn_readlane(xl, k));
+            const double yk = __hiloint2double(__builtin_amdgcn_readlane(yh, k), __builtin_amdgcn_readlane(yl, k));
+            const uint32_t c = (k & 1) ? (t.c[k >> 1] >> 16) : (t.c[k >> 1] & 0xffffu);
+            atomicAdd(&acc[c & ((1u << kRowBits) - 1)], (c & (1u << kRowBits)) ? yk : xk);
+        }
+    };
+    Rd dA, dB;
+    Gt tA, tB;
+    load(dA, 0);
+    load(dB, 1);
+    issue(dA, tA);
+    __builtin_amdgcn_sched_barrier(0);
+    load(dA, 2);
+    int32_t k = 1;
+    for (; k + 1 < nr; k += 2) {
+        __builtin_amdgcn_sched_barrier(0);
+        issue(dB, tB);
+        __builtin_amdgcn_sched_barrier(0);
+        load(dB, k + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        add(tA);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(dA, tA);
+        __builtin_amdgcn_sched_barrier(0);
+        load(dA, k + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        add(tB);
+    }
+    if (k < nr) {
+        issue(dB, tB);
+        add(tA);
+        add(tB);
+    } else {
+        add(tA);
+    }
+}
+
 // One iteration's SpMV over split blocks.  Work items: [0, nlong_pad) LONG row segments (padded
 // to a multiple of 8), then the units (largest first; the blocks of rows without entries last).  A multi-unit block's units store their row sums write-through (sc1) to
 // their own slab, drain them (vmcnt(0)) and take a ticket; the last arriver adds the slabs in
@@ -641,6 +739,7 @@ __device__ __forceinline__ void pull_item(const SortedArgs &a, const uint32_t w,
     if (!empty) {
         for (int i = tid; i < nrows; i += kBS) acc[i] = 0.0;
         __syncthreads();
+        gather_runs<CP>(a, u, acc);
         gather_pairs<CP>(a, u, acc);
         gather_narrow<CP>(a, u, acc);
         gather_units<CP>(a, b, u.lo, u.hi, acc, u.step);
@@ -1033,10 +1132,12 @@ __global__ __launch_bounds__(256) void k_sorted_laneperm(const RowBlock *__restr
     }
 }
 
-// Bank-aware order inside column runs (GX_PR_BANK_ORDER; gx_pr_bank.h), for the pair prefix
+// Bank-aware order inside column runs (GX_PR_BANK_ORDER; gx_pr_bank.h), for the run region
+// (supergroups below rsplit[block]: runs of one column pair, in plain positions: a run's codes
+// are consecutive from a group's start), the pair prefix
 // (supergroups below qsplit[block]: runs of one column pair) and the narrow prefix (up to
 // nsplit[block]: runs of one column) of every sorted block, before their codes are emitted.  In
-// both layouts a 16-lane group of an LDS add covers 16 consecutive codes (slots), and a run has no
+// all three layouts a 16-lane group of an LDS add covers 16 consecutive codes (slots), and a run has no
 // filler inside it, so consecutive entries of a run meet in a group.  Each piece of a run inside
 // a tile of kBankTile entries is dealt round-robin over its rows' classes (row mod 16), in place.
 // A piece keeps its entries (row and column move together), so the block's multiset of
@@ -1053,13 +1154,15 @@ __global__ __launch_bounds__(256) void k_sorted_laneperm(const RowBlock *__restr
 // matter to the banks.  A tile may straddle the end of the pair prefix; a piece does not.  The
 // words of spk keep the column offset of the supergroup they came from, which neither prefix reads.
 constexpr int kBankTile = 2048, kBankBS = 256, kBankPer = kBankTile / kBankBS;
-__global__ __launch_bounds__(kBankBS) void k_bank_order(const RowBlock *__restrict__ blocks, const uint32_t *__restrict__ qsplit,
+__global__ __launch_bounds__(kBankBS) void k_bank_order(const RowBlock *__restrict__ blocks, const uint32_t *__restrict__ rsplit,
+                                                        const uint32_t *__restrict__ qsplit,
                                                         const uint32_t *__restrict__ nsplit, uint32_t *spk, int32_t *sci) {
     __shared__ uint32_t cnt2[kBankTile / 2][kBankClasses / 2];   // 32 KiB
     __shared__ int32_t wred[2][kBankBS / kWave];
     const RowBlock b = blocks[blockIdx.y];
     const int64_t z0 = b.nz_begin, N = b.nz_end - z0;
     const int64_t Nq = min(N, (int64_t)qsplit[blockIdx.y] << 8), Np = min(N, (int64_t)nsplit[blockIdx.y] << 8);
+    const int64_t Nr = min(N, (int64_t)rsplit[blockIdx.y] << 8);   // run region: keyed by pair, plain positions
     const int64_t ntiles = (Np + kBankTile - 1) / kBankTile;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     for (int64_t g = blockIdx.x; g < ntiles; g += gridDim.x) {
@@ -1088,8 +1191,8 @@ __global__ __launch_bounds__(kBankBS) void k_bank_order(const RowBlock *__restri
 #pragma unroll
         for (int j = 0; j < kBankPer; j++) {
             const int32_t i = i0 + j;
-            // the tile's first entry, the narrow prefix's first, an entry past the prefix, a new key
-            head[j] = i == 0 || i >= nin || t0 + i == Nq || key[j] != (j ? key[j - 1] : prevkey);
+            // the tile's first entry, the pair or narrow prefix's first, an entry past the prefix, a new key
+            head[j] = i == 0 || i >= nin || t0 + i == Nq || t0 + i == Nr || key[j] != (j ? key[j - 1] : prevkey);
             if (head[j]) last = i;
             s0[j] = last;
         }
@@ -1142,8 +1245,8 @@ __global__ __launch_bounds__(kBankBS) void k_bank_order(const RowBlock *__restri
                 cnt[2 * k + 1] = w >> 16;
             }
             const uint32_t k = bank_deal_pos(cnt, p[j] & (uint32_t)(kBankClasses - 1), rank[j]);
-            const bool pairs = t0 + s0[j] < Nq;
-            const int64_t dst = z0 + t0 + s0[j] + (pairs ? bank_pair_pos(k, n) : k);
+            const bool pairs = t0 + s0[j] < Nq, runs = t0 + s0[j] < Nr;
+            const int64_t dst = z0 + t0 + s0[j] + (pairs && !runs ? bank_pair_pos(k, n) : k);
             spk[dst] = p[j];
             if (pairs) sci[dst] = c[j];   // a narrow run is one column
         }
@@ -1336,25 +1439,29 @@ struct PairLane {
     bool in[4], start[4], lead[4], half[4];
 };
 
+// The first entry of the column-pair run that holds entry f of a block (z0): f itself, or, when
+// the run starts before it, found by binary search (the entries are column-sorted).  Uniform over
+// the wave when f is.
+__device__ __forceinline__ int64_t pair_run_start(const int32_t *__restrict__ sci, int64_t z0, int64_t f) {
+    const uint32_t pf = (uint32_t)sci[z0 + f] >> 1;
+    if (f == 0 || ((uint32_t)sci[z0 + f - 1] >> 1) != pf) return f;
+    int64_t lo = 0, hi = f;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (((uint32_t)sci[z0 + mid] >> 1) >= pf) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 __device__ __forceinline__ void pair_lane(const int32_t *__restrict__ sci, int64_t z0, int64_t N, int64_t Nq, int64_t g,
                                           int lane, PairLane &o) {
     const int64_t i0 = (g << 8) + 4 * lane;
     uint32_t c[6];   // the entry before, the four, the entry after
 #pragma unroll
     for (int j = 0; j < 6; j++) c[j] = (uint32_t)sci[z0 + min(max(i0 + j - 1, (int64_t)0), N - 1)];
-    // the run holding the supergroup's first entry starts before it: found by binary search
     const int64_t f = g << 8;
-    const uint32_t pf = (uint32_t)sci[z0 + f] >> 1;
-    int64_t gs = f;
-    if (f > 0 && ((uint32_t)sci[z0 + f - 1] >> 1) == pf) {   // uniform
-        int64_t lo = 0, hi = f;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (((uint32_t)sci[z0 + mid] >> 1) >= pf) hi = mid;
-            else lo = mid + 1;
-        }
-        gs = lo;
-    }
+    const int64_t gs = pair_run_start(sci, z0, f);
     int32_t ls = -1;   // the last run start among the lane's entries (supergroup-relative)
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -1387,11 +1494,14 @@ __device__ __forceinline__ void pair_lane(const int32_t *__restrict__ sci, int64
     }
 }
 
-// Slots and filler halves of every 256-entry supergroup of every sorted block.
+// Slots and filler halves of every 256-entry supergroup of every sorted block from the end of its
+// run region rsplit[block] on (the slots start afresh there).
 __global__ __launch_bounds__(256) void k_pair_cost(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
-                                                   uint32_t *__restrict__ slots, uint32_t *__restrict__ fill) {
+                                                   const uint32_t *__restrict__ rsplit, uint32_t *__restrict__ slots,
+                                                   uint32_t *__restrict__ fill) {
     const RowBlock b = blocks[blockIdx.y];
-    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, ng = (N + 255) >> 8;
+    const int64_t R = rsplit[blockIdx.y];
+    const int64_t z0 = b.nz_begin + (R << 8), N = b.nz_end - z0, ng = (N + 255) >> 8;   // past the run region
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
     for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < ng; g += waves) {
@@ -1406,8 +1516,8 @@ __global__ __launch_bounds__(256) void k_pair_cost(const RowBlock *__restrict__ 
         ns = wave_total(ns);
         nf = wave_total(nf);
         if (lane == 0) {
-            slots[b.seg + g] = ns;
-            fill[b.seg + g] = nf;
+            slots[b.seg + R + g] = ns;
+            fill[b.seg + R + g] = nf;
         }
     }
 }
@@ -1423,18 +1533,21 @@ __global__ void k_pair_fill(uint32_t *__restrict__ ppk, uint64_t nslots, uint32_
     if (blockIdx.x == 0 && threadIdx.x == 0) pbase[null_sg] = zero_pair;
 }
 
-// The slots of the pair prefix: one wave per 256-entry supergroup g < Q of each block; lane l
+// The slots of the pair prefix: one wave per 256-entry supergroup R <= g < Q of each block; lane l
 // emits the slots led by entries 4l .. 4l+3, each run's first preceded by its filler slots, at
 // the block's run + poff[g] + the lane's exclusive scan of slot counts.  Whoever emits the last
 // slot of a 256-slot supergroup stores the next one's base (the pair reached); the block's first
 // base is its first pair.  nfill: the filler halves written (statistics).
 __global__ __launch_bounds__(256) void k_pair_emit(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
-                                                   const uint32_t *__restrict__ spk, const uint32_t *__restrict__ qsplit,
+                                                   const uint32_t *__restrict__ spk, const uint32_t *__restrict__ rsplit,
+                                                   const uint32_t *__restrict__ qsplit,
                                                    const uint32_t *__restrict__ pcount, const uint32_t *__restrict__ poff,
                                                    const int64_t *__restrict__ pbeg, uint32_t *__restrict__ ppk,
                                                    uint32_t *__restrict__ pbase, unsigned long long *__restrict__ nfill) {
     const RowBlock b = blocks[blockIdx.y];
-    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, Q = qsplit[blockIdx.y];
+    // supergroups and entries counted from the end of the run region
+    const int64_t R = rsplit[blockIdx.y];
+    const int64_t z0 = b.nz_begin + (R << 8), N = b.nz_end - z0, Q = (int64_t)qsplit[blockIdx.y] - R;
     const int64_t Nq = min(N, Q << 8);
     const int64_t pb = pbeg[blockIdx.y], C = pcount[blockIdx.y];
     const int lane = threadIdx.x & (kWave - 1);
@@ -1450,7 +1563,7 @@ __global__ __launch_bounds__(256) void k_pair_emit(const RowBlock *__restrict__ 
             n += (pl.lead[j] ? 1u : 0u) + (pl.start[j] ? pl.sf[j] : 0u);
             nf += (pl.half[j] ? 1u : 0u) + (pl.start[j] ? 2 * pl.sf[j] : 0u);
         }
-        int64_t pos = pb + poff[b.seg + g] + (wave_scan_incl(n) - n);   // absolute slot index
+        int64_t pos = pb + poff[b.seg + R + g] + (wave_scan_incl(n) - n);   // absolute slot index
         nf = wave_total(nf);
         if (lane == 0 && nf) atomicAdd(nfill, (unsigned long long)nf);
         // stored lane-major inside the 256-slot supergroup: slot e of it at (e mod 64) * 4 + e / 64
@@ -1478,6 +1591,123 @@ __global__ __launch_bounds__(256) void k_pair_emit(const RowBlock *__restrict__ 
             const uint32_t hb = pl.half[j] ? (uint32_t)(kJunkRow + (pos & (kWave - 1)))
                                            : ((pl.next[j] & 1u) << kRowBits) | (spk[z0 + e + 1] & kRowMask);
             put(step, ha, hb, pl.pair[j]);
+        }
+    }
+}
+
+// ---- run groups (gather_runs, gx_pr_runs.h).  The first R 256-entry supergroups of a block's
+// column-sorted entries are recoded as 2-byte run codes.  The entries of a column pair are
+// consecutive (a run); a run's codes start on a group of 64 and the run is followed by
+// run_pad(its length) padding codes, so the entry at sorted position e takes code position
+// e + (the padding of the runs that end before e).  The padding of a run is counted in the
+// supergroup that holds its last entry, so a supergroup's count does not depend on R; the run
+// that R cuts is padded like the others (run_region_codes).
+
+// The lane's four entries 4 lane .. 4 lane + 3 of supergroup g of a block (z0, N entries, the
+// first Nr of them in the region), one wave per supergroup: where a run ends (or the region cuts
+// it), the run's length.
+struct RunLane {
+    uint32_t pair[4], col[4], len[4];   // len: the run's entries at its last entry, 0 elsewhere
+    bool in[4];
+};
+
+__device__ __forceinline__ void run_lane(const int32_t *__restrict__ sci, int64_t z0, int64_t N, int64_t Nr, int64_t g,
+                                         int lane, RunLane &o) {
+    const int64_t i0 = (g << 8) + 4 * lane;
+    uint32_t c[6];   // the entry before, the four, the entry after
+#pragma unroll
+    for (int j = 0; j < 6; j++) c[j] = (uint32_t)sci[z0 + min(max(i0 + j - 1, (int64_t)0), N - 1)];
+    const int64_t f = g << 8;
+    const int64_t gs = pair_run_start(sci, z0, f);
+    bool start[4];
+    int32_t ls = -1;   // the last run start among the lane's entries (supergroup-relative)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int64_t i = i0 + j;
+        o.in[j] = i < Nr;
+        o.col[j] = c[j + 1];
+        o.pair[j] = c[j + 1] >> 1;
+        start[j] = o.in[j] && (i == 0 || (c[j] >> 1) != o.pair[j]);
+        if (start[j]) ls = 4 * lane + j;
+    }
+    int32_t m = ls;   // inclusive max scan over the lanes
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int32_t v = __shfl_up(m, d, kWave);
+        if (lane >= d) m = max(m, v);
+    }
+    int32_t before = __shfl_up(m, 1, kWave);
+    if (lane == 0) before = -1;
+    int64_t rs = before >= 0 ? f + before : gs;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int64_t i = i0 + j;
+        if (start[j]) rs = i;
+        const bool end = o.in[j] && (i + 1 >= Nr || (c[j + 2] >> 1) != o.pair[j]);
+        o.len[j] = end ? (uint32_t)(i - rs + 1) : 0u;
+    }
+}
+
+// Padding codes of every 256-entry supergroup of every sorted block.
+__global__ __launch_bounds__(256) void k_run_cost(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
+                                                  uint32_t *__restrict__ fill) {
+    const RowBlock b = blocks[blockIdx.y];
+    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, ng = (N + 255) >> 8;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < ng; g += waves) {
+        RunLane rl;
+        run_lane(sci, z0, N, N, g, lane, rl);
+        RunCursor cur{0};   // the padding of the runs that end among the lane's entries
+#pragma unroll
+        for (int j = 0; j < 4; j++) cur.end_run(rl.len[j]);
+        const uint32_t nf = wave_total((uint32_t)cur.pad);
+        if (lane == 0) fill[b.seg + g] = nf;
+    }
+}
+
+// Padding codes everywhere (sel 0, a junk row by lane) and every group's pair the one holding x's
+// zero slot: the groups after a block's last run and the null supergroup gather 0.0.
+__global__ void k_run_fill(uint16_t *__restrict__ rpk, uint64_t ncodes, uint32_t *__restrict__ rpair, uint32_t zero_pair) {
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < ncodes; p += (uint64_t)gridDim.x * blockDim.x) {
+        rpk[p] = (uint16_t)(kJunkRow + ((p / kRunSgGroups) & (kWave - 1)));
+        if ((p & (kRunGroup - 1)) == 0) rpair[p / kRunGroup] = zero_pair;
+    }
+}
+
+// The codes of the run region: one wave per 256-entry supergroup g < R of each block; lane l
+// emits entries 4l .. 4l+3 at the block's run + roff[g] (the codes before the supergroup's first
+// entry) + the entry's offset + the padding of the runs that end in the supergroup before it.  The
+// entry whose code opens a group stores the group's pair, so no header past the block's last
+// group is written.
+__global__ __launch_bounds__(256) void k_run_emit(const RowBlock *__restrict__ blocks, const int32_t *__restrict__ sci,
+                                                  const uint32_t *__restrict__ spk, const uint32_t *__restrict__ rsplit,
+                                                  const uint32_t *__restrict__ roff, const int64_t *__restrict__ rbeg,
+                                                  uint16_t *__restrict__ rpk, uint32_t *__restrict__ rpair) {
+    const RowBlock b = blocks[blockIdx.y];
+    const int64_t z0 = b.nz_begin, N = b.nz_end - z0, R = rsplit[blockIdx.y];
+    const int64_t Nr = min(N, R << 8);
+    const int64_t rb = rbeg[blockIdx.y];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t waves = (int64_t)gridDim.x * blockDim.x / kWave;
+    for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; g < R; g += waves) {
+        RunLane rl;
+        run_lane(sci, z0, N, Nr, g, lane, rl);
+        RunCursor lanepad{0};
+#pragma unroll
+        for (int j = 0; j < 4; j++) lanepad.end_run(rl.len[j]);
+        const uint32_t n = (uint32_t)lanepad.pad;
+        // the padding before the lane's first entry: the block's codes before the supergroup's first
+        // entry, less those entries themselves, and the runs that end in the lanes before
+        RunCursor cur{(uint64_t)roff[b.seg + g] - (uint64_t)(g << 8) + (wave_scan_incl(n) - n)};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int64_t e = (g << 8) + 4 * lane + j;
+            if (!rl.in[j]) continue;
+            const uint64_t pos = (uint64_t)rb + cur.place((uint64_t)e);   // absolute code index
+            rpk[run_slot(pos)] = (uint16_t)(((rl.col[j] & 1u) << kRowBits) | (spk[z0 + e] & ((1u << kRowBits) - 1)));
+            if ((pos & (kRunGroup - 1)) == 0) rpair[run_group_of(pos)] = rl.pair[j];
+            cur.end_run(rl.len[j]);
         }
     }
 }
@@ -1697,6 +1927,9 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     p->ncodes = 0;
     p->nnarrow = 0;
     p->npair = p->npfill = p->npslots = 0;
+    p->nrun = p->nrpad = p->nrcodes = 0;
+    std::vector<uint32_t> h_rsplit(sortb.size(), 0), h_rcode(sortb.size(), 0);   // run region per sorted block
+    std::vector<int64_t> h_rbeg(sortb.size(), 0);
     // Pair slots (GX_PR_PAIRS; gather_pairs).  Every mode (interleaved units, work queue, slab
     // combine, GX_PR_COMBINE=1) takes the pair rounds as it takes the narrow ones.  The slots
     // need an even chunk (a pair never straddles two
@@ -1707,6 +1940,10 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     // (DESIGN.md 4).
     const bool pairs_on = env_int("GX_PR_PAIRS", huge && !piece ? 1 : 0, 0, 1) == 1;
     if (pairs_on && (p->chunk & 1)) return fail(GX_INVALID_VALUE, "pr_plan_sorted: pair slots need an even chunk");
+    // Run groups (GX_PR_RUNS; gather_runs): the same conditions as the pair slots, and on by default
+    // where they are
+    const bool runs_on = env_int("GX_PR_RUNS", huge && !piece ? 1 : 0, 0, 1) == 1;
+    if (runs_on && (p->chunk & 1)) return fail(GX_INVALID_VALUE, "pr_plan_sorted: run groups need an even chunk");
     // device temporaries of the plan, released after the unit-size search (which runs on the
     // host while the narrow codes and the lane permutation are built)
     DBuf<int32_t> d_seg_row;
@@ -1719,6 +1956,8 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     DBuf<uint32_t> d_pslots, d_pfill, d_poff, d_psplit, d_pcount;
     DBuf<int64_t> d_pbeg;
     DBuf<unsigned long long> d_npfill;
+    DBuf<uint32_t> d_rfill, d_roff, d_rsplit, d_rcode;
+    DBuf<int64_t> d_rbeg;
     if (nnz > 0) {
         // segments in row order: the sorted blocks and the LONG rows
         std::vector<std::pair<int32_t, int32_t>> order_;   // (first row, index: block i >= 0, LONG row -1 - j)
@@ -1848,16 +2087,37 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             GX_TRY(d_pcount.alloc(nsb));
             GX_TRY(d_pbeg.alloc(nsb));
             GX_TRY(d_npfill.alloc(1));
-            GX_HIP_TRY(hipMemsetAsync(d_psplit.p, 0, nsb * 4, s));
             GX_HIP_TRY(hipMemsetAsync(d_npfill.p, 0, sizeof(unsigned long long), s));
+            // the run regions R first: the prefix of supergroups maximising entries - w padding codes
+            // (w = GX_PR_RUN_FILL_COST / 4 entries per padding code), in blocks of at least
+            // GX_PR_RUN_MIN entries; the pair slots then start at R.  Off: R = 0 everywhere
+            GX_TRY(d_rsplit.alloc(nsb));
+            GX_HIP_TRY(hipMemsetAsync(d_rsplit.p, 0, nsb * 4, s));
+            if (runs_on) {
+                GX_TRY(d_rfill.alloc(std::max<int64_t>(ngroups, 1)));
+                GX_TRY(d_roff.alloc(std::max<int64_t>(ngroups, 1)));
+                GX_TRY(d_rcode.alloc(nsb));
+                GX_TRY(d_rbeg.alloc(nsb));
+                hipLaunchKernelGGL(k_run_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_rfill.p);
+                GX_TRY(check_launch("k_run_cost"));
+                hipLaunchKernelGGL(k_narrow_split, dim3(nsb), dim3(1024), 0, s, d_sort, d_rfill.p, (const uint32_t *)nullptr,
+                                   env_int("GX_PR_RUN_FILL_COST", kRunFillCost, 0, 1 << 20), (const uint32_t *)nullptr, 1,
+                                   (int64_t)env_int("GX_PR_RUN_MIN", 65536, 0, 1 << 30), d_rsplit.p, d_rcode.p, d_roff.p);
+                GX_TRY(check_launch("k_narrow_split (runs)"));
+                GX_HIP_TRY(hipMemcpyAsync(h_rsplit.data(), d_rsplit.p, nsb * 4, hipMemcpyDeviceToHost, s));
+                GX_HIP_TRY(hipMemcpyAsync(h_rcode.data(), d_rcode.p, nsb * 4, hipMemcpyDeviceToHost, s));
+            }
+            // (without pair slots the pair prefix is empty: Q = R)
+            GX_HIP_TRY(hipMemcpyAsync(d_psplit.p, d_rsplit.p, nsb * 4, hipMemcpyDeviceToDevice, s));
             if (pairs_on) {
                 GX_TRY(d_pslots.alloc(std::max<int64_t>(ngroups, 1)));
                 GX_TRY(d_pfill.alloc(std::max<int64_t>(ngroups, 1)));
                 GX_TRY(d_poff.alloc(std::max<int64_t>(ngroups, 1)));
-                hipLaunchKernelGGL(k_pair_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_pslots.p, d_pfill.p);
+                hipLaunchKernelGGL(k_pair_cost, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, d_rsplit.p, d_pslots.p,
+                                   d_pfill.p);
                 GX_TRY(check_launch("k_pair_cost"));
                 hipLaunchKernelGGL(k_narrow_split, dim3(nsb), dim3(1024), 0, s, d_sort, d_pfill.p, d_pslots.p,
-                                   env_int("GX_PR_PAIR_FILL_COST", 48, 0, 1 << 20), (const uint32_t *)nullptr, 1,
+                                   env_int("GX_PR_PAIR_FILL_COST", 48, 0, 1 << 20), d_rsplit.p, 1,
                                    (int64_t)env_int("GX_PR_PAIR_MIN", 0, 0, 1 << 30), d_psplit.p, d_pcount.p, d_poff.p);
                 GX_TRY(check_launch("k_narrow_split (pairs)"));
                 GX_HIP_TRY(hipMemcpyAsync(h_psplit.data(), d_psplit.p, nsb * 4, hipMemcpyDeviceToHost, s));
@@ -1872,26 +2132,51 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             GX_HIP_TRY(hipMemcpyAsync(h_nsplit.data(), d_nsplit.p, nsb * 4, hipMemcpyDeviceToHost, s));
             GX_HIP_TRY(hipMemcpyAsync(h_ncode.data(), d_ncode.p, nsb * 4, hipMemcpyDeviceToHost, s));
             GX_HIP_TRY(hipStreamSynchronize(s));
-            uint64_t run = 0, prun = 0;
+            if (!pairs_on) h_psplit = h_rsplit;
+            uint64_t run = 0, prun = 0, rrun = 0;
             for (size_t i = 0; i < sortb.size(); i++) {
                 const int64_t E = sortb[i].nz_end - sortb[i].nz_begin;
-                const int64_t Ep = std::min<int64_t>((int64_t)h_psplit[i] * 256, E);
+                const int64_t Er = std::min<int64_t>((int64_t)h_rsplit[i] * 256, E);   // in run codes
+                const int64_t Ep = std::min<int64_t>((int64_t)h_psplit[i] * 256, E);   // run codes + pair slots
+                // the region's codes: the run that R cuts is padded like the others
+                h_rcode[i] = (uint32_t)run_region_codes(h_rcode[i]);
+                h_rbeg[i] = (int64_t)rrun;
+                rrun += ((uint64_t)h_rcode[i] + kRunSg - 1) / kRunSg * kRunSg;
+                p->nrun += (uint64_t)Er;
+                p->nrpad += (uint64_t)h_rcode[i] - (uint64_t)Er;
                 h_nbeg[i] = (int64_t)run;
                 run += ((uint64_t)h_ncode[i] + kNSg - 1) / kNSg * kNSg;
                 p->nnarrow += (uint64_t)(std::min<int64_t>((int64_t)h_nsplit[i] * 256, E) - Ep);
                 h_pbeg[i] = (int64_t)prun;
                 prun += ((uint64_t)h_pcount[i] + kPSg - 1) / kPSg * kPSg;
-                p->npair += (uint64_t)Ep;
+                p->npair += (uint64_t)(Ep - Er);
             }
             // the order inside the runs of both prefixes, now that they are known, before their codes
             // (GX_PR_BANK_ORDER=0: ascending rows, as the stable sort leaves them).  On where the pair
             // slots are on by default, the huge graph's single plan
             if (env_int("GX_PR_BANK_ORDER", huge && !piece ? 1 : 0, 0, 1) == 1) {
                 clk.mark("prefix splits");
-                hipLaunchKernelGGL(k_bank_order, dim3(64, nsb), dim3(kBankBS), 0, s, d_sort, d_psplit.p, d_nsplit.p, p->spk.p,
-                                   p->sci.p);
+                hipLaunchKernelGGL(k_bank_order, dim3(64, nsb), dim3(kBankBS), 0, s, d_sort, d_rsplit.p, d_psplit.p, d_nsplit.p,
+                                   p->spk.p, p->sci.p);
                 GX_TRY(check_launch("k_bank_order"));
                 clk.mark("bank order");
+            }
+            // the run codes: padding everywhere, then each block's region
+            if (runs_on) {
+                p->rnull_sg = (uint32_t)(rrun / kRunSg);
+                p->nrcodes = rrun + kRunSg;
+                GX_TRY(p->rpk.alloc(p->nrcodes, 16));
+                GX_TRY(p->rpair.alloc(p->nrcodes / kRunGroup));
+                hipLaunchKernelGGL(k_run_fill, dim3(grid_for(p->nrcodes, 256, 16384)), dim3(256), 0, s, p->rpk.p, p->nrcodes,
+                                   p->rpair.p, (uint32_t)((p->chunk - 2) >> 1));
+                GX_TRY(check_launch("k_run_fill"));
+                if (p->nrun) {
+                    GX_HIP_TRY(hipMemcpyAsync(d_rbeg.p, h_rbeg.data(), nsb * 8, hipMemcpyHostToDevice, s));
+                    hipLaunchKernelGGL(k_run_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_rsplit.p,
+                                       d_roff.p, d_rbeg.p, p->rpk.p, p->rpair.p);
+                    GX_TRY(check_launch("k_run_emit"));
+                }
+                clk.mark("run codes");
             }
             // the pair slots: padding everywhere, then each block's prefix
             p->pnull_sg = (uint32_t)(prun / kPSg);
@@ -1903,7 +2188,7 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
             GX_TRY(check_launch("k_pair_fill"));
             if (p->npair) {
                 GX_HIP_TRY(hipMemcpyAsync(d_pbeg.p, h_pbeg.data(), nsb * 8, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(k_pair_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_psplit.p,
+                hipLaunchKernelGGL(k_pair_emit, dim3(64, nsb), dim3(256), 0, s, d_sort, p->sci.p, p->spk.p, d_rsplit.p, d_psplit.p,
                                    d_pcount.p, d_poff.p, d_pbeg.p, p->ppk.p, p->pbase.p, d_npfill.p);
                 GX_TRY(check_launch("k_pair_emit"));
                 unsigned long long nf = 0;
@@ -1958,14 +2243,19 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
     // GX_PR_PAIR_COST: an entry held in a pair slot, in quarters of a narrow entry's cost (its
     // filler halves, where the codes are priced, at the same rate)
     const int64_t pair_cost4 = env_int("GX_PR_PAIR_COST", 4, 1, 64);
+    // GX_PR_RUN_COST: a run code, padding included, in quarters of a narrow entry's cost
+    const int64_t run_cost4 = env_int("GX_PR_RUN_COST", kRunCost, 1, 64);
     auto eff_entries = [&](int64_t i) -> int64_t {
         const int64_t E = sortb[i].nz_end - sortb[i].nz_begin;
-        const int64_t Ep = std::min<int64_t>(E, 256 * (int64_t)h_psplit[i]);       // in pair slots
-        const int64_t Enp = std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]);      // pair slots + narrow codes
-        const int64_t En = Enp - Ep;
+        const int64_t Er = std::min<int64_t>(E, 256 * (int64_t)h_rsplit[i]);       // in run codes
+        const int64_t Erp = std::min<int64_t>(E, 256 * (int64_t)h_psplit[i]);      // run codes + pair slots
+        const int64_t Ep = Erp - Er;
+        const int64_t Enp = std::min<int64_t>(E, 256 * (int64_t)h_nsplit[i]);      // ... + narrow codes
+        const int64_t En = Enp - Erp;
         const int64_t fill = cost_codes ? std::max<int64_t>(0, (int64_t)h_ncode[i] - En) : 0;
         const int64_t pent = cost_codes ? std::max<int64_t>(Ep, 2 * (int64_t)h_pcount[i]) : Ep;
-        return pent * pair_cost4 / 4 + En + fill * fill_cost4 / 4 + (E - Enp) * wide_cost4 / 4;
+        return (int64_t)h_rcode[i] * run_cost4 / 4 + pent * pair_cost4 / 4 + En + fill * fill_cost4 / 4 +
+               (E - Enp) * wide_cost4 / 4;
     };
     // huge graphs: units per block by weighted entries (GX_PR_UNIT_BY_COST=0: by entries), so a
     // block of mostly wide entries, ~half the hub blocks' entry rate, is cut into more units
@@ -2096,7 +2386,8 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
                 u.nsg = (int32_t)(((int64_t)h_ncode[i] + kNSg - 1) / kNSg);
                 u.pbeg = h_pbeg[i];
                 u.psg = (int32_t)(((int64_t)h_pcount[i] + kPSg - 1) / kPSg);
-                u.pad = 0;
+                u.rbeg = h_rbeg[i];
+                u.rsg = (int32_t)(((int64_t)h_rcode[i] + kRunSg - 1) / kRunSg);
                 u.seg = b.seg;
                 u.z0 = b.nz_begin;
                 u.z1 = b.nz_end;
@@ -2166,7 +2457,8 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
         if (env_int("GX_PR_VERBOSE", 0, 0, 3) && pairs_on) {
             size_t nq = 0;
             uint64_t qsum = 0;
-            for (uint32_t q : h_psplit) {
+            for (size_t i = 0; i < h_psplit.size(); i++) {
+                const uint32_t q = h_psplit[i] - h_rsplit[i];
                 nq += q > 0;
                 qsum += q;
             }
@@ -2174,6 +2466,18 @@ int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg
                          "%zu of %zu blocks with a pair prefix, mean Q %.1f supergroups\n",
                          (unsigned long long)p->npair, (unsigned long long)p->npfill, (unsigned long long)p->npslots, nq,
                          h_psplit.size(), nq ? (double)qsum / (double)nq : 0.0);
+        }
+        if (env_int("GX_PR_VERBOSE", 0, 0, 3)) {
+            size_t nq = 0;
+            uint64_t rsum = 0;
+            for (uint32_t q : h_rsplit) {
+                nq += q > 0;
+                rsum += q;
+            }
+            std::fprintf(stderr, "[gx_pr] runs: %llu entries and %llu padding codes in %llu codes (supergroup padding "
+                         "included); %zu of %zu blocks with a run prefix, mean R %.1f supergroups\n",
+                         (unsigned long long)p->nrun, (unsigned long long)p->nrpad, (unsigned long long)p->nrcodes, nq,
+                         h_rsplit.size(), nq ? (double)rsum / (double)nq : 0.0);
         }
         GX_TRY(p->units.alloc(units.size()));
         GX_HIP_TRY(hipMemcpy(p->units.p, units.data(), units.size() * sizeof(SortedUnit), hipMemcpyHostToDevice));
@@ -2280,9 +2584,12 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
     a.ppk = p->ppk.p;
     a.pbase = p->pbase.p;
     a.pnull_sg = p->pnull_sg;
+    a.rpk = p->rpk.p;
+    a.rpair = p->rpair.p;
+    a.rnull_sg = p->rnull_sg;
     // a pair slot's one load reads x[2p] and x[2p + 1]
-    if (p->npair && (reinterpret_cast<uintptr_t>(x_full) & 15))
-        return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots need x 16-byte aligned");
+    if ((p->npair || p->nrun) && (reinterpret_cast<uintptr_t>(x_full) & 15))
+        return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots and run groups need x 16-byte aligned");
     a.queue = p->queue.p;
     // Isolated rows in closed form: a launch whose scores nobody asks for leaves the closed-form
     // blocks (the last iso_units items, the last iso_dblocks dangling slots) out and has the
@@ -2348,6 +2655,8 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
                         for (int64_t k0 = u.lo; k0 < u.hi; k0 += u.step) ents += std::min<int64_t>(u.step / u.nunits, u.hi - k0);
                         for (int64_t r = u.unit; r * 16 < u.nsg; r += u.nunits)   // narrow codes (fillers included)
                             ents += std::min<int64_t>(16, u.nsg - r * 16) * kNSg;
+                        for (int64_t r = u.unit; r * 16 < u.rsg; r += u.nunits)   // run codes (padding included)
+                            ents += std::min<int64_t>(16, u.rsg - r * 16) * kRunSg;
                         for (int64_t r = u.unit; r * 16 < u.psg; r += u.nunits)   // pair slots, two entries each
                             ents += std::min<int64_t>(16, u.psg - r * 16) * kPSg * 2;
                         blk = u.blk;
