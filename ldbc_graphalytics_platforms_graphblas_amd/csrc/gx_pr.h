@@ -263,7 +263,7 @@ struct HostView {
 int pr_plan(PrPart *p, HostView<int64_t> h_rp, const int64_t *d_rp,
             const int32_t *d_ci, const int32_t *d_outdeg, HostView<int32_t> h_outdeg);
 
-// Column-sorted block plan (k_pr_pull_units) and its iteration (gx_pr_sorted.hip).
+// Column-sorted block plan (gx_pr_plan.hip) and its iteration (k_pr_pull_units, gx_pr_sorted.hip).
 int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg);
 int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s);
 // Dangling-score sum of this rank into x_local's last chunk slot.
@@ -273,9 +273,47 @@ int pr_init(PrPart *p, double *x_local, hipStream_t s);
 // gx_pagerank's single-rank plan of a graph: its pull matrix (A' when directed, which must be
 // built) relabelled hub-first, column-sorted blocks, x buffers and the hub-first perm.
 int pr_single_plan(gx_graph *g, PrPart **out);
-// Rows of a huge graph's sorted block (gx_pr_sorted.hip kMaxBlockRows) and its entries.
+// Rows of a huge graph's sorted block (kMaxBlockRows below) and its entries.
 constexpr int kPlanBlockRows = 16320;
 constexpr int64_t kPlanBlockNnz = 32 << 20;
+
+// What the sorted-block iteration (gx_pr_sorted.hip) and its plan (gx_pr_plan.hip) share: the
+// geometry of a k_pr_pull_units workgroup and of the code regions, which the plan lays the tables
+// out for and the kernel decodes.
+constexpr int kRowBits = 14;     // packed entry: (column - group base) << kRowBits | row in block
+constexpr int kBS = 1024;        // threads of a k_pr_pull_units workgroup (16 waves, one per CU)
+constexpr int kCombBS = 256;     // threads of a k_pr_combine workgroup: rows of a stripe
+constexpr int kU = 8;            // entries per lane and round (two 16-B index loads)
+constexpr int kRound = kBS * kU; // entries of one round of a workgroup
+constexpr int kNSg = 512;        // codes of a narrow supergroup: one wave's 16-B load per lane
+constexpr int kPSg = 256;        // slots of a pair supergroup: one wave's 16-B load per lane
+constexpr int kRunFillCost = 32;  // GX_PR_RUN_FILL_COST: quarters of an entry per padding code
+constexpr int kRunCost = 2;       // GX_PR_RUN_COST: quarters of a narrow entry's cost per run code
+constexpr int kJunkRow = (1 << kRowBits) - kWave;   // accumulators [16320, 16384) absorb fillers
+constexpr int kMaxBlockRows = kJunkRow;             // rows of a sorted block
+static_assert(kMaxBlockRows == kPlanBlockRows, "gx_pr.h block rows");
+
+// Inclusive prefix sum over the 64 lanes by DPP moves (row_shr 1/2/4/8 inside each 16-lane
+// row, then row_bcast:15 and row_bcast:31 across rows); lanes whose source is out of range or
+// whose row is masked add the `old` operand, 0.
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+    return v;
+}
+
+// An integer knob from the environment: dflt when unset or outside [lo, hi].
+inline int env_int(const char *name, int dflt, int lo, int hi) {
+    if (const char *e = std::getenv(name)) {
+        const int v = std::atoi(e);
+        if (v >= lo && v <= hi) return v;
+    }
+    return dflt;
+}
 
 // gx_pagerank_multi's block partition (pr_partition.block_relabel restated): the hub-first
 // order cut into the single-GPU plan's blocks, dealt whole to the devices largest first (LPT);

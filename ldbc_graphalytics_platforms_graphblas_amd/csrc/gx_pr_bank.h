@@ -1,5 +1,5 @@
 // gx_pr_bank.h -- the bank-aware order inside a column run of a sorted block (GX_PR_BANK_ORDER,
-// k_bank_order in gx_pr_sorted.hip).  Plain C++ so that a host test can call it.
+// k_bank_order in gx_pr_plan.hip).  Plain C++ so that a host test can call it.
 //
 // A 64-bit LDS add is served in groups of 16 consecutive lanes, and two rows of one group
 // collide when they are equal mod 16 (their bank slot class).  The entries of one

@@ -1,5 +1,5 @@
 // gx_pr_runs.h -- the layout arithmetic of the run region of a sorted block (GX_PR_RUNS; k_run_cost,
-// k_run_emit and gather_runs in gx_pr_sorted.hip).  Plain C++ so that a host test can call it.
+// k_run_emit in gx_pr_plan.hip, gather_runs in gx_pr_sorted.hip).  Plain C++ so that a host test can call it.
 //
 // The region holds the block's first column-sorted entries, one 2-byte code each.  The entries of
 // one column pair (columns 2p and 2p + 1) are consecutive, a run; a run's codes start on a group

@@ -143,7 +143,7 @@ def _deal_blocks(work: np.ndarray, live: np.ndarray, nparts: int, owner: np.ndar
 def block_relabel(csr: CSR, nparts: int, rows_per_block: int = 16320, block_nnz: int = 32 << 20):
     """The single-GPU plan's sorted blocks dealt whole over `nparts` parts: the hub-first order
     cut greedily into blocks of at most `rows_per_block` rows and `block_nnz` entries (as
-    pr_plan_sorted cuts a huge graph, gx_pr_sorted.hip), the blocks dealt heaviest first
+    pr_plan_sorted cuts a huge graph, gx_pr_plan.hip), the blocks dealt heaviest first
     (_deal_blocks: work, then live rows), and each part's blocks kept in hub-first order as one
     contiguous id range.  Unlike interleaved_relabel, whose parts hold every nparts-th hub-first
     row (so a part's 16 Ki-row block spans nparts x as many hub positions and shares each x line

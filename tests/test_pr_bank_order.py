@@ -1,5 +1,5 @@
 """PageRank's bank-aware order inside column runs (GX_PR_BANK_ORDER; k_bank_order,
-gx_pr_sorted.hip) and the isolated rows in closed form (GX_PR_ISO_CLOSED).  Every GPU case runs
+gx_pr_plan.hip) and the isolated rows in closed form (GX_PR_ISO_CLOSED).  Every GPU case runs
 with the knob on and off, each against the fp64 oracle at the parity bar of
 tests/test_gpu_parity.py, and the two against each other; the deal itself and the model's counts
 are checked on the CPU."""

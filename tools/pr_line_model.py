@@ -20,7 +20,7 @@ sys.path.insert(0, str(ROOT))
 
 
 def blocks_of(rp, B, R):
-    """pr_plan_sorted's cut: runs of rows with <= B entries and <= R rows; rows > B are LONG."""
+    """pr_plan_sorted's cut (gx_pr_plan.hip cut_blocks): runs of rows with <= B entries and <= R rows; rows > B are LONG."""
     rows = len(rp) - 1
     out, long_rows = [], []
     r = 0

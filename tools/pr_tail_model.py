@@ -21,7 +21,7 @@ sys.path.insert(0, str(ROOT))
 
 
 def cut(rp, B, R):
-    """Runs of <= B entries and <= R rows (pr_plan_sorted's sorted blocks; no LONG rows here)."""
+    """Runs of <= B entries and <= R rows (pr_plan_sorted's sorted blocks, gx_pr_plan.hip cut_blocks; no LONG rows here)."""
     n = len(rp) - 1
     out = []
     r = 0
