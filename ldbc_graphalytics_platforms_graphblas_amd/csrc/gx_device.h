@@ -432,6 +432,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 namespace gx {
 hipError_t warm_bfs(hipStream_t s);
 hipError_t warm_cdlp(hipStream_t s);
+hipError_t warm_cdlp_keep(hipStream_t s);
+hipError_t warm_cdlp_tiers(hipStream_t s);
 hipError_t warm_lcc(hipStream_t s);
 hipError_t warm_ops(hipStream_t s);
 hipError_t warm_part(hipStream_t s);
