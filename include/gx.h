@@ -127,6 +127,22 @@ int gx_bfs(gx_graph *g, uint64_t src, int64_t *level);
  * GX_MIN_SECONDI_INT64 loop below.  The levels come from gx_bfs's traversal; one more pass over
  * the edges derives the parents from them.  Counts as a BFS call on g (transpose, copy). */
 int gx_bfs_parent(gx_graph *g, uint64_t src, int64_t *level, int64_t *parent);
+/* The role of LAGraph_MultiSourceBFS: the levels of ns traversals, GX_MSBFS_BATCH sources per pass
+ * over the edges (bit k of one 64-bit word per vertex is source k of the batch), sources taken in
+ * the order given, the last batch possibly partial.  level is ns * n int64 or NULL: row k is what
+ * gx_bfs(g, sources[k], ..) returns, bit for bit.  stats is 3 * ns uint64 or NULL: for source k,
+ * stats[3k] = the vertices reached (the source included), stats[3k+1] = the sum of their levels,
+ * stats[3k+2] = the largest level; with level == NULL only these cross the host link (what
+ * closeness and eccentricity need).  Integer sums only: the same bit for bit on every run.  A
+ * source listed twice gives two equal rows; ns == 0 succeeds and writes nothing.
+ * NULL g, NULL sources with ns > 0, or level and stats both NULL: GX_NULL_POINTER; a source >= n:
+ * GX_INVALID_INDEX; all before any device work, the outputs untouched.  Always runs on g itself
+ * (never the hub-first copy) and does not count as a BFS call on g: the gx_bfs calls around it take
+ * the paths they would have taken without it.  Builds and caches the transpose of a directed graph.
+ * GX_MSBFS_ALPHA: a level pushes (atomics from the frontier's out-rows) while the frontier's
+ * out-edges are at most nnz / alpha, else pulls; GX_MSBFS_DIR=push|pull forces one form. */
+#define GX_MSBFS_BATCH 64
+int gx_msbfs(gx_graph *g, const uint64_t *sources, uint64_t ns, int64_t *level, uint64_t *stats);
 
 /* The role of LAGr_Betweenness(&centrality, G, sources, ns): Brandes' dependency accumulation from a
  * batch of sources, one after the other.  For a source s, with hop levels over out-edges as gx_bfs

@@ -61,6 +61,7 @@ SIGNATURES = [
     ("gx_graph_info", C.c_int, [_P, _U64P, _U64P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("gx_bfs", C.c_int, [_P, C.c_uint64, _I64P]),
     ("gx_bfs_parent", C.c_int, [_P, C.c_uint64, _I64P, _I64P]),
+    ("gx_msbfs", C.c_int, [_P, _U64P, C.c_uint64, _I64P, _U64P]),
     ("gx_betweenness", C.c_int, [_P, _U64P, C.c_uint64, _DP, _DP]),
     ("gx_pagerank", C.c_int, [_P, C.c_double, C.c_int, _DP]),
     ("gx_sssp", C.c_int, [_P, C.c_uint64, _DP]),

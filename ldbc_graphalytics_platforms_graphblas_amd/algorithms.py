@@ -114,6 +114,24 @@ def LA_BFS_parent(G: Graph, source_vertex: int):
     return level, parent
 
 
+MSBFS_BATCH = 64   # GX_MSBFS_BATCH: sources per pass over the edges
+
+
+def LA_MSBFS(G: Graph, sources, levels: bool = True, stats: bool = False):
+    """The role of LAGraph_MultiSourceBFS (gx_msbfs): level[ns, n] int64, row k as LA_BFS(G, sources[k]);
+    stats[ns, 3] uint64 = (vertices reached, sum of their levels, largest level) per source; or both
+    as a tuple.  With levels=False only the statistics leave the device; asking for neither is
+    gx_msbfs's GX_NULL_POINTER."""
+    src = np.ascontiguousarray(sources, dtype=np.uint64).reshape(-1)
+    lev = np.empty((len(src), G.n), dtype=np.int64) if levels else None
+    st = np.zeros((len(src), 3), dtype=np.uint64) if stats else None
+    N.check(N.lib().gx_msbfs(G.handle, N.as_u64p(src) if len(src) else None, len(src),
+                             N.as_i64p(lev) if levels else None, N.as_u64p(st) if stats else None), "gx_msbfs")
+    if levels and stats:
+        return lev, st
+    return lev if levels else st
+
+
 # gx_betweenness's row tiers (gx_bfs.hip kBcShort / kBcLong): a row of at most BC_SHORT entries is
 # one thread's, of at most BC_LONG one wave's, a longer one a workgroup's; GX_BC_SHORT / GX_BC_LONG override.
 # GX_BC_BITS: rows a level bucket needs to probe a level bitmap instead of the levels (0 always, -1 never)

@@ -435,6 +435,7 @@ hipError_t warm_cdlp(hipStream_t s);
 hipError_t warm_cdlp_keep(hipStream_t s);
 hipError_t warm_cdlp_tiers(hipStream_t s);
 hipError_t warm_lcc(hipStream_t s);
+hipError_t warm_msbfs(hipStream_t s);
 hipError_t warm_ops(hipStream_t s);
 hipError_t warm_part(hipStream_t s);
 hipError_t warm_sssp_split(hipStream_t s);
