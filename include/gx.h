@@ -162,6 +162,42 @@ int gx_msbfs(gx_graph *g, const uint64_t *sources, uint64_t ns, int64_t *level, 
  * (never the hub-first copy); builds and caches the transpose of a directed graph. */
 int gx_betweenness(gx_graph *g, const uint64_t *sources, uint64_t ns, double *centrality, double *paths);
 
+/* The role of LAGraph_KTruss(&C, G, k).  The graph must be undirected with both directions stored.
+ * An edge is an unordered pair {i, j}, i != j; the k-truss is the largest subgraph in which every
+ * edge lies in at least k - 2 triangles of that subgraph (it is unique).  Diagonal entries belong to
+ * no edge and to no truss.
+ * support is nnz int64 in A's entry order (as gx_mxm_masked orders its output) or NULL: for the entry
+ * (i, j) the number of triangles of the k-truss that contain {i, j}, -1 when the edge is not in the
+ * k-truss, -1 for a diagonal entry; both stored directions of an edge carry the same value.  stats is
+ * uint64[3] or NULL: stats[0] = the edges of the k-truss (pairs, not entries), stats[1] = its
+ * triangles, stats[2] = the rounds of synchronous pruning that removed at least one edge, round r
+ * removing every edge whose support in the graph left by round r - 1 is below k - 2 (LAGraph's loop;
+ * the count does not depend on which supports the implementation chose to recount).  With support ==
+ * NULL only the three statistics cross the host link.  k == 2 keeps every edge: support is then the
+ * triangle support on the whole graph, which on a graph without diagonal entries is gx_mxm_masked's
+ * output.  nnz == 0 succeeds and writes zero statistics.
+ * NULL g, or support and stats both NULL: GX_NULL_POINTER; a directed graph, k < 2, or a stored
+ * (i, j) whose (j, i) is not stored (found on the device while the reverse positions are built;
+ * a row that repeats a column fails the same way): GX_INVALID_VALUE; nnz >= 2^32:
+ * GX_NOT_IMPLEMENTED; all before any output is written.
+ * Runs on g itself (never the hub-first copy) and counts as no BFS, WCC or SSSP call on g; the
+ * sorted view of A, the reverse positions and the work buffers are built by the first call and kept
+ * with g until gx_graph_free.  Integers only: the same bit for bit on every run.
+ * An edge belongs to the entry with i < j; by the shorter of rows i and j it is counted by one
+ * thread (at most GX_TRUSS_SHORT entries), one wave (at most GX_TRUSS_LONG) or one workgroup.  After
+ * a round only the edges that lost a triangle are recounted, unless the round removed more than
+ * GX_TRUSS_SHARE percent of the alive edges; GX_TRUSS_RECOUNT=all|marked forces one form (the
+ * results are identical).  GX_TRUSS_VERBOSE prints one line per round to stderr. */
+int gx_ktruss(gx_graph *g, uint32_t k, int64_t *support, uint64_t *stats);
+/* The role of LAGraph_AllKTruss: every k at once, as one number per edge.  truss is nnz int64 in A's
+ * entry order or NULL: the largest k such that the entry's edge is in the k-truss (>= 2 for every
+ * off-diagonal entry, 0 for a diagonal one), so truss[e] >= k exactly when gx_ktruss(g, k, ..) gives
+ * support[e] >= 0.  kmax (may be NULL, not both) is the largest entry of truss, 0 when there is no
+ * edge.  One support count of the whole graph, then k = 3, 4, ...: pruning to a fixed point at each k
+ * with the flags and supports carried over; what dies while pruning for k gets k - 1.  Graph, errors,
+ * cache and knobs as gx_ktruss. */
+int gx_truss_all(gx_graph *g, int64_t *truss, uint64_t *kmax);
+
 /* LAGr_PageRankGX(&r, &iters, G, damping, itermax) incl. LAGraph_Cached_OutDegree /
  * LAGraph_Cached_AT (pr.cpp:58-61).  Graphalytics PR with dangling redistribution,
  * exactly `iters` iterations, fp64. */

@@ -150,6 +150,39 @@ def LA_BC(G: Graph, sources, return_paths: bool = False):
     return (out, paths) if return_paths else out
 
 
+# gx_ktruss / gx_truss_all's row tiers (gx_truss.hip kTrussShort / kTrussLong): an edge whose shorter row
+# has at most TRUSS_SHORT entries is counted by one thread, at most TRUSS_LONG by one wave, a longer one
+# by a workgroup; GX_TRUSS_SHORT / GX_TRUSS_LONG override.  GX_TRUSS_RECOUNT=all|marked forces what a
+# round recounts, GX_TRUSS_SHARE the percentage of removed edges above which it recounts everything.
+TRUSS_SHORT, TRUSS_LONG = 16, 1024
+
+
+def LA_KTruss(G: Graph, k: int, support: bool = True, stats: bool = False):
+    """The role of LAGraph_KTruss (gx_ktruss) on an undirected graph: support[nnz] int64 in the CSR's
+    entry order, the triangles of the k-truss through the entry's edge, -1 where the edge is not in
+    the k-truss (and on the diagonal); stats[3] uint64 = (edges, triangles, pruning rounds); or both
+    as a tuple.  With support=False only the statistics leave the device; asking for neither is
+    gx_ktruss's GX_NULL_POINTER."""
+    if not 0 <= int(k) < 2 ** 32:
+        raise ValueError("k does not fit uint32")
+    sup = np.empty(max(G.nnz, 1), dtype=np.int64) if support else None
+    st = np.zeros(3, dtype=np.uint64) if stats else None
+    N.check(N.lib().gx_ktruss(G.handle, int(k), N.as_i64p(sup) if support else None,
+                              N.as_u64p(st) if stats else None), "gx_ktruss")
+    if support and stats:
+        return sup[:G.nnz], st
+    return sup[:G.nnz] if support else st
+
+
+def LA_AllKTruss(G: Graph):
+    """The role of LAGraph_AllKTruss (gx_truss_all): (truss, kmax); truss[nnz] int64 in the CSR's entry
+    order = the largest k whose k-truss holds the entry's edge (0 on the diagonal), kmax its maximum."""
+    truss = np.empty(max(G.nnz, 1), dtype=np.int64)
+    kmax = C.c_uint64(0)
+    N.check(N.lib().gx_truss_all(G.handle, N.as_i64p(truss), C.byref(kmax)), "gx_truss_all")
+    return truss[:G.nnz], int(kmax.value)
+
+
 def LA_PR(G: Graph, damping_factor: float, iteration_num: int) -> np.ndarray:
     """pr.cpp:47-66: Graphalytics PageRank, fp64."""
     out = np.empty(G.n, dtype=np.float64)

@@ -219,6 +219,7 @@ struct gx_graph {
     gx::SsspLayout *sssp = nullptr;   // cached light/heavy edge layout
     std::shared_ptr<void> cdlp;       // gx_cdlp's tier lists and buffers (gx_cdlp.hip CdlpCache)
     std::shared_ptr<void> lcc;        // gx_lcc's orientation and work items (gx_lcc.hip LccCache)
+    std::shared_ptr<void> truss;      // gx_ktruss / gx_truss_all's view, tiers and state (gx_truss.hip TrussCache)
     // Hub-first relabelled copy of an undirected graph (gx_runtime.hip hub_for): BFS, WCC and
     // SSSP run on it from their second call on the graph.  perm[v] = v's id in the copy, order
     // its inverse; on the copy, out_perm / out_order point at the parent's perm / order.
@@ -444,5 +445,6 @@ hipError_t warm_pr_plan(hipStream_t s);
 hipError_t warm_pr_sorted(hipStream_t s);
 hipError_t warm_runtime(hipStream_t s);
 hipError_t warm_sssp(hipStream_t s);
+hipError_t warm_truss(hipStream_t s);
 hipError_t warm_wcc(hipStream_t s);
 }  // namespace gx
