@@ -175,7 +175,6 @@ struct SsspLayout {
     DBuf<int32_t> ci;
     DBuf<double> w;
     DBuf<int64_t> lend;   // end of the light part of row v (absolute entry index)
-    int64_t n_active = 0; // vertices with at least one edge
     std::shared_ptr<void> work;   // gx_sssp's work buffers and captured step graph (gx_sssp.hip)
 };
 }  // namespace gx
@@ -210,7 +209,10 @@ struct gx_graph {
     gx::DevCSR A, AT, S;
     gx::DBuf<int32_t> outdeg;   // out-degree of every vertex (PR)
     gx::PrPart *pr = nullptr;   // cached single-rank PageRank plan
-    double mean_w = -1.0;       // cached mean edge weight (SSSP bucket width), < 0 = not yet computed
+    // SSSP's per-graph numbers (sssp_graph_stats, gx_sssp.h), < 0 = not yet computed: the mean edge
+    // weight (bucket width) and the vertices with at least one edge (pull threshold)
+    double mean_w = -1.0;
+    int64_t nonisolated = -1;
     int bfs_calls = 0;          // BFS runs on this graph (a directed graph builds A^T from the second)
     int bfs_steps_hint = 0;     // device-driven level steps the last BFS took (gx_bfs first batch)
     gx::DBuf<int32_t> wcc_ids;  // Afforest's sampled vertices (+ one word: the giant root)

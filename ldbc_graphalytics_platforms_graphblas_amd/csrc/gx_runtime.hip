@@ -637,7 +637,6 @@ int build_hub(gx_graph *g) {
     c->nnz = g->nnz;
     c->directed = false;
     c->weighted = g->weighted;
-    c->mean_w = g->mean_w;
     c->A.n = g->n;
     c->A.nnz = g->nnz;
     c->A.h_rp.assign(n + 1, 0);

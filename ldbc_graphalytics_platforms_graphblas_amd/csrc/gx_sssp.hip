@@ -22,6 +22,10 @@
 // Scheduling runs on the device: a one-thread plan kernel reads the queue counts and picks
 // the next action (relax / open the next ring bucket / split the overflow / done), so the
 // host launches plan -> advance -> relax triples in batches and syncs once per batch.
+//
+// The knobs and the per-graph rules (bucket width, pull threshold, fusion bound), shared with
+// gx_sssp_split.hip, are declared in gx_sssp.h and defined here; gx_sssp() at the end of the
+// file is the list of a call's stages.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -32,28 +36,14 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "gx_device.h"
+#include "gx_sssp.h"
 
 namespace gx {
 namespace {
 
 constexpr int kSsspBlock = 256;
-constexpr int kChunk = 256;
-constexpr int kRing = 32;
 constexpr uint32_t kOob = 0x80000000u;   // buffer offset past every record: the lane is dropped
 constexpr int64_t kMaxBufVertices = (int64_t)(kOob / 8u);   // dist[] must stay below kOob bytes
-
-__device__ __forceinline__ unsigned long long dbits(double d) {
-    return (unsigned long long)__double_as_longlong(d);
-}
-__device__ __forceinline__ double bitsd(unsigned long long b) { return __longlong_as_double((long long)b); }
-
-__device__ __forceinline__ uint32_t chunks_of(int64_t deg) { return (uint32_t)((deg + kChunk - 1) / kChunk); }
-
-__device__ __forceinline__ int64_t bucket_of(double d, double inv_delta) {
-    const double q = d * inv_delta;
-    return q < 4.0e18 ? (int64_t)q : (int64_t)4000000000000000000ll;
-}
 
 struct SsspState {
     int64_t cur;                  // bucket being settled
@@ -345,7 +335,7 @@ __global__ void k_sssp_plan(SsspState *st) {
         st->split_src = src;
         st->epoch++;
         st->ovf_cnt[st->epoch & 1] = 0;
-        const int64_t mb = (int64_t)min(st->ovf_minb, 4000000000000000000ull);
+        const int64_t mb = (int64_t)min(st->ovf_minb, (unsigned long long)kMaxBucket);
         st->win_base = max(st->cur + 1, mb);
         st->cur = st->win_base - 1;
         st->ovf_minb = ~0ull;
@@ -968,12 +958,6 @@ int ensure_sssp_layout(gx_graph *g, double delta, hipStream_t s) {
     const int64_t n = (int64_t)g->n, nnz = (int64_t)g->nnz;
     auto L = std::make_unique<SsspLayout>();
     L->delta = delta;
-    L->n_active = n;
-    GX_TRY(ensure_host_rp(g->ctx, g->A));
-    if ((int64_t)g->A.h_rp.size() == n + 1) {
-        L->n_active = 0;
-        for (int64_t v = 0; v < n; v++) L->n_active += g->A.h_rp[v + 1] != g->A.h_rp[v];
-    }
     GX_TRY(L->ci.alloc(nnz, 16));
     GX_TRY(L->w.alloc(nnz, 16));
     GX_TRY(L->lend.alloc(n));
@@ -1017,6 +1001,76 @@ int ensure_sssp_layout(gx_graph *g, double delta, hipStream_t s) {
     g->sssp = L.release();
     return GX_SUCCESS;
 }
+
+// Per-block partial sums of the weights in a fixed order (grid-stride per thread, butterfly per
+// wave, waves in index order), so the bucket width derived from them is bitwise the same on
+// every rank that holds the same graph, and from run to run: the ranks' scheduling decisions
+// must agree.
+__global__ __launch_bounds__(256) void k_sssp_sum_w(const double *__restrict__ w, int64_t m, double *part) {
+    __shared__ double wsum[256 / kWave];
+    double acc = 0.0;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < m; k += (int64_t)gridDim.x * 256) acc += w[k];
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < 256 / kWave; i++) t += wsum[i];
+        part[blockIdx.x] = t;
+    }
+}
+
+}  // namespace
+
+// ---- the per-graph rules of both SSSP paths (gx_sssp.h) ----
+
+int sssp_graph_stats(gx_graph *g, hipStream_t s) {
+    if (g->mean_w >= 0.0 && g->nonisolated >= 0) return GX_SUCCESS;
+    double mean = 1.0;
+    if (g->nnz) {
+        const unsigned grid = grid_for(g->nnz, 256, 4096);
+        DBuf<double> part;
+        GX_TRY(part.alloc(grid));
+        hipLaunchKernelGGL(k_sssp_sum_w, dim3(grid), dim3(256), 0, s, g->A.w.p, (int64_t)g->nnz, part.p);
+        GX_TRY(check_launch("k_sssp_sum_w"));
+        std::vector<double> h(grid);
+        GX_HIP_TRY(hipMemcpyAsync(h.data(), part.p, grid * sizeof(double), hipMemcpyDeviceToHost, s));
+        GX_HIP_TRY(hipStreamSynchronize(s));
+        double t = 0.0;
+        for (double x : h) t += x;   // block order: deterministic for a given graph
+        mean = t / (double)g->nnz;
+    }
+    GX_TRY(ensure_host_rp(g->ctx, g->A));
+    const HostRowPtr &rp = g->A.h_rp;
+    int64_t nonisolated = 0;
+    for (int64_t v = 0; v < (int64_t)g->n; v++) nonisolated += rp[v + 1] != rp[v];
+    g->mean_w = mean;
+    g->nonisolated = nonisolated;
+    return GX_SUCCESS;
+}
+
+// delta = scale * mean weight / mean degree, unless GX_SSSP_DELTA gives it
+double sssp_delta(const gx_graph *g, const SsspKnobs &k) {
+    double delta = k.delta;
+    if (!(delta > 0.0)) delta = k.dscale * g->mean_w / std::max(1.0, (double)g->nnz / std::max(1.0, (double)g->n));
+    if (!(delta > 0.0) || !std::isfinite(delta)) delta = 1.0;
+    return delta;
+}
+
+uint32_t sssp_pull_min(const gx_graph *g, const SsspKnobs &k) {
+    if (k.pull == 2) return 1u;
+    if (k.pull == 0 || !(k.pull_frac > 0.0)) return k.split ? 0u : 0xFFFFFFFFu;
+    const double share = (double)g->nonisolated / k.pull_frac;
+    return (uint32_t)std::max(1.0, k.split ? std::floor(share) : std::ceil(share));
+}
+
+uint32_t sssp_fuse(const gx_graph *g, const SsspKnobs &k) {
+    if (k.split)
+        return k.fuse_set ? (uint32_t)std::max<long long>(1, k.fuse) : (uint32_t)std::max<int64_t>(1024, (int64_t)g->n / 16);
+    return k.fuse_set ? (uint32_t)k.fuse : 0xFFFFFFFFu;
+}
+
+namespace {
 
 // Work buffers of gx_sssp, kept with the graph's light/heavy layout so repeated runs reuse
 // them, and the captured graph of kGraphSteps plan -> advance -> relax steps (its kernel
@@ -1064,6 +1118,35 @@ struct SsspWork {
         GX_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         return GX_SUCCESS;
     }
+    // The kernels' argument for a run on g's layout with these buffers.
+    SsspBufs bufs(const gx_graph *g, double delta, unsigned long long *stats, uint32_t dense_div) const {
+        const SsspLayout &lay = *g->sssp;
+        SsspBufs B{};
+        B.rp = g->A.rp.p;
+        B.lend = lay.lend.p;
+        B.ci = lay.ci.p;
+        B.w = lay.w.p;
+        B.dist = dist.p;
+        B.relaxed = relaxed.p;
+        B.nsw = nsw.p;
+        B.bstamp = bstamp.p;
+        B.ostamp = ostamp.p;
+        B.sbits = sbits.p;
+        B.nbits = nbit_words((int64_t)g->n);
+        B.q[0] = q0.p;
+        B.q[1] = q1.p;
+        B.ring = ring.p;
+        B.ovf[0] = ovf0.p;
+        B.ovf[1] = ovf1.p;
+        B.settled = settled.p;
+        B.ring_cap = g->n;
+        B.delta = delta;
+        B.inv_delta = 1.0 / delta;
+        B.st = st.p;
+        B.stats = stats;
+        B.dense_div = dense_div;
+        return B;
+    }
     int enqueue_steps(const SsspBufs &B, unsigned grid, int k, hipStream_t s) {
         for (int i = 0; i < k; i++) {
             hipLaunchKernelGGL(k_sssp_plan, dim3(1), dim3(1), 0, s, B.st);
@@ -1074,6 +1157,9 @@ struct SsspWork {
     }
     // The captured kernels hold B by value: every member, pointer or scalar (delta, dense_div,
     // ...), is part of the capture's key.  Compared member by member (the struct has padding).
+    static_assert(sizeof(SsspBufs) == 184,
+                  "SsspBufs changed: add the new member to SsspWork::bufs and to same_bufs below, or a captured "
+                  "step graph is replayed with stale arguments");
     static bool same_bufs(const SsspBufs &a, const SsspBufs &b) {
         return a.rp == b.rp && a.lend == b.lend && a.ci == b.ci && a.w == b.w && a.dist == b.dist &&
                a.relaxed == b.relaxed && a.nsw == b.nsw && a.bstamp == b.bstamp && a.ostamp == b.ostamp &&
@@ -1106,11 +1192,213 @@ struct SsspWork {
     }
 };
 
-__global__ __launch_bounds__(256) void k_sum_weights(const double *__restrict__ w, int64_t m, double *sum) {
-    double acc = 0.0;
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < m; k += (int64_t)gridDim.x * 256) acc += w[k];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(sum, acc);
+// GX_SSSP_VERBOSE: the kernels' work counters (wave_count's slots) and, for the per-step log, the
+// two events that time a step.
+struct SsspCounters {
+    DBuf<unsigned long long> stats;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    unsigned long long prev[8] = {};   // the totals at the last per-step line
+    ~SsspCounters() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    int init(int level, hipStream_t s) {
+        if (level < 1) return GX_SUCCESS;
+        GX_TRY(stats.alloc(8 * kStatLanes));
+        GX_HIP_TRY(hipMemsetAsync(stats.p, 0, 8 * kStatLanes * sizeof(unsigned long long), s));
+        if (level < 2) return GX_SUCCESS;
+        GX_HIP_TRY(hipEventCreate(&ev0));
+        GX_HIP_TRY(hipEventCreate(&ev1));
+        return GX_SUCCESS;
+    }
+    // Every counter summed over its lanes; synchronises s.
+    int totals(unsigned long long (&c)[8], hipStream_t s) {
+        std::vector<unsigned long long> raw(8 * kStatLanes);
+        GX_HIP_TRY(hipMemcpyAsync(raw.data(), stats.p, raw.size() * sizeof(raw[0]), hipMemcpyDeviceToHost, s));
+        GX_HIP_TRY(hipStreamSynchronize(s));
+        std::fill(c, c + 8, 0ull);
+        for (int i = 0; i < 8 * kStatLanes; i++) c[i / kStatLanes] += raw[i];
+        return GX_SUCCESS;
+    }
+    // GX_SSSP_VERBOSE=2: the step planned as h, timed between ev0 and ev1, and what it added to the counters.
+    int step_line(uint64_t step, const SsspState &h, hipStream_t s) {
+        unsigned long long c[8];
+        GX_TRY(totals(c, s));
+        float ms = 0.f;
+        GX_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        std::fprintf(stderr, "step %llu round %d bucket %lld mode %d heavy %d pull %d near %u settled %u | %.1f us "
+                     "items %llu edges %llu improved %llu near %llu ring %llu\n",
+                     (unsigned long long)step, h.round, (long long)h.cur, h.mode, h.heavy, h.pull,
+                     h.qcnt[h.round & 1], h.settled_cnt, ms * 1e3, c[0] - prev[0], c[1] - prev[1],
+                     c[3] - prev[3], c[4] - prev[4], c[5] - prev[5]);
+        std::memcpy(prev, c, sizeof(c));
+        return GX_SUCCESS;
+    }
+    int summary_line(double delta, uint64_t steps, const SsspState *st, hipStream_t s) {
+        SsspState h;
+        GX_HIP_TRY(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+        unsigned long long c[8];
+        GX_TRY(totals(c, s));
+        std::fprintf(stderr,
+                     "gx_sssp: delta %g rounds %d last bucket %lld epochs %d launched steps %llu | items %llu edges "
+                     "%llu tried %llu improved %llu near %llu ring %llu ovf %llu skipped %llu\n",
+                     delta, h.round, (long long)h.cur, h.epoch, (unsigned long long)steps, c[0], c[1], c[2], c[3],
+                     c[4], c[5], c[6], c[7]);
+        return GX_SUCCESS;
+    }
+};
+
+// One gx_sssp call on the graph it runs on (the caller's, or its hub-first copy).
+struct SsspCall {
+    gx_graph *g;
+    gx_ctx *ctx;
+    hipStream_t s;
+    int64_t n;
+    int32_t src;
+    SsspKnobs k;
+    double delta = 0.0;
+    SsspCounters cnt;
+    SsspWork *W = nullptr;
+    SsspBufs B{};
+    unsigned grid = 0;
+    uint64_t max_steps = 0;      // a bound every correct run stays far below: each step settles a vertex or a bucket
+    uint64_t steps = 0;          // plan -> advance -> relax steps launched
+    const void *res = nullptr;   // the distances to download (set once remapped)
+    SsspCall(gx_graph *g_, uint64_t src_)
+        : g(g_), ctx(g_->ctx), s(g_->ctx->stream), n((int64_t)g_->n), src((int32_t)src_) {}
+    int check_bound() const {
+        return steps > max_steps ? fail(GX_PANIC, "gx_sssp: delta-stepping did not converge") : GX_SUCCESS;
+    }
+};
+
+int sssp_check_args(const gx_graph *g, uint64_t src, const double *dist_out) {
+    if (!g || !dist_out) return fail(GX_NULL_POINTER, "gx_sssp: null argument");
+    if (!g->weighted) return fail(GX_INVALID_VALUE, "gx_sssp: graph has no edge weights");
+    if (src >= g->n) return fail(GX_INVALID_INDEX, "gx_sssp: source out of range");
+    if ((int64_t)g->n >= kMaxBufVertices)
+        return fail(GX_NOT_IMPLEMENTED, "gx_sssp: more than 2^28 vertices (buffer-load offsets are 31-bit)");
+    return GX_SUCCESS;
+}
+
+// The layout for this call's delta and the work buffers kept with it.  The device-time bracket
+// (gx_last_device_ms) opens here and closes in sssp_finish; a failed call leaves the last
+// successful call's time in place, so the pair is not a scope guard.
+int sssp_prepare(SsspCall &c) {
+    GX_TRY(c.cnt.init(c.k.verbose, c.s));
+    GX_TRY(device_begin(c.ctx));
+    {
+        KTimer kt(c.ctx, "sssp_layout", c.s);
+        GX_TRY(ensure_sssp_layout(c.g, c.delta, c.s));
+    }
+    SsspLayout &lay = *c.g->sssp;
+    if (!lay.work) {
+        auto w = std::make_shared<SsspWork>();
+        GX_TRY(w->alloc(c.n, (uint64_t)c.n + c.g->nnz / kChunk + 64));
+        lay.work = w;
+    }
+    c.W = static_cast<SsspWork *>(lay.work.get());
+    return GX_SUCCESS;
+}
+
+int sssp_seed(SsspCall &c) {
+    SsspWork &W = *c.W;
+    hipLaunchKernelGGL(k_sssp_init, dim3(grid_for(c.n, 256, 8192)), dim3(256), 0, c.s, W.dist.p, W.relaxed.p, W.nsw.p,
+                       W.bstamp.p, W.ostamp.p, c.n);
+    GX_TRY(check_launch("k_sssp_init"));
+    hipLaunchKernelGGL(k_sssp_seed, dim3(1), dim3(256), 0, c.s, c.B, c.src, sssp_pull_min(c.g, c.k),
+                       sssp_fuse(c.g, c.k), c.k.fuse_max);
+    GX_TRY(check_launch("k_sssp_seed"));
+    c.grid = (unsigned)std::max(1, c.ctx->num_cus) * 8;
+    c.max_steps = 8ull * (uint64_t)c.n + 4ull * (uint64_t)c.g->nnz + 1000000ull;
+    return GX_SUCCESS;
+}
+
+// Replayed step graph: one replay always queued behind the one whose done flag is read.  The
+// first batch is as many replays as the last run on this layout needed; when that was enough,
+// the remap to the caller's order (hub-first copy) is queued behind it instead of an idle
+// replay, and runs while the host reads the flag.
+int run_replayed(SsspCall &c) {
+    SsspWork &W = *c.W;
+    hipStream_t s = c.s;
+    GX_TRY(W.capture(c.B, c.grid, s));
+    // capped, so that one long run (a deep chain) cannot queue many idle replays for the next
+    const int hint = std::min(W.replays_hint, 12);
+    auto read_state = [&]() -> int {
+        GX_HIP_TRY(hipMemcpyAsync(W.h_done, &W.st.p->round, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GX_HIP_TRY(hipEventRecord(W.ev, s));
+        return GX_SUCCESS;
+    };
+    for (int i = 0; i < std::max(1, hint); i++) GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
+    c.steps += (uint64_t)std::max(1, hint) * kGraphSteps;
+    GX_TRY(read_state());
+    if (hint > 0) {
+        GX_TRY(remap_out(c.g, W.dist.p, 8, s, &c.res));
+    } else {
+        GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
+        c.steps += kGraphSteps;
+    }
+    GX_HIP_TRY(hipEventSynchronize(W.ev));
+    if (!W.h_done[1]) c.res = nullptr;
+    while (!W.h_done[1]) {
+        GX_TRY(read_state());
+        GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
+        GX_HIP_TRY(hipEventSynchronize(W.ev));
+        c.steps += kGraphSteps;
+        GX_TRY(c.check_bound());
+    }
+    W.replays_hint = (W.h_done[0] + kGraphSteps) / kGraphSteps;   // round + 1 plan steps ran
+    return GX_SUCCESS;
+}
+
+// Batches of 4, 8, .. 32 steps, the done flag read after each (kernel timing, GX_SSSP_VERBOSE=1,
+// GX_SSSP_GRAPH=0).
+int run_batched(SsspCall &c) {
+    int32_t done = 0;
+    for (int batch = 4; !done; batch = std::min(batch * 2, 32)) {
+        for (int i = 0; i < batch; i++) {
+            hipLaunchKernelGGL(k_sssp_plan, dim3(1), dim3(1), 0, c.s, c.B.st);
+            {
+                KTimer kt(c.ctx, "sssp_advance", c.s);
+                hipLaunchKernelGGL(k_sssp_advance, dim3(c.grid), dim3(kSsspBlock), 0, c.s, c.B);
+            }
+            {
+                KTimer kt(c.ctx, "sssp_relax", c.s);
+                hipLaunchKernelGGL(k_sssp_relax, dim3(c.grid), dim3(kSsspBlock), 0, c.s, c.B);
+            }
+        }
+        GX_TRY(check_launch("k_sssp_relax"));
+        c.steps += batch;
+        GX_HIP_TRY(hipMemcpyAsync(&done, &c.B.st->done, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        GX_HIP_TRY(hipStreamSynchronize(c.s));
+        GX_TRY(c.check_bound());
+    }
+    return GX_SUCCESS;
+}
+
+// GX_SSSP_VERBOSE=2: one step at a time, a line per step (bucket, phase, items, work, time).
+int run_per_step(SsspCall &c) {
+    int32_t done = 0;
+    while (!done) {
+        hipLaunchKernelGGL(k_sssp_plan, dim3(1), dim3(1), 0, c.s, c.B.st);
+        SsspState h;
+        GX_HIP_TRY(hipMemcpyAsync(&h, c.B.st, sizeof(h), hipMemcpyDeviceToHost, c.s));
+        GX_HIP_TRY(hipEventRecord(c.cnt.ev0, c.s));
+        hipLaunchKernelGGL(k_sssp_advance, dim3(c.grid), dim3(kSsspBlock), 0, c.s, c.B);
+        hipLaunchKernelGGL(k_sssp_relax, dim3(c.grid), dim3(kSsspBlock), 0, c.s, c.B);
+        GX_HIP_TRY(hipEventRecord(c.cnt.ev1, c.s));
+        GX_HIP_TRY(hipMemcpyAsync(&done, &c.B.st->done, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        GX_TRY(c.cnt.step_line(c.steps, h, c.s));
+        c.steps++;
+        GX_TRY(c.check_bound());
+    }
+    return GX_SUCCESS;
+}
+
+int sssp_finish(SsspCall &c, double *dist_out) {
+    if (!c.res) GX_TRY(remap_out(c.g, c.W->dist.p, 8, c.s, &c.res));
+    GX_TRY(device_end(c.ctx));
+    if (c.k.verbose) GX_TRY(c.cnt.summary_line(c.delta, c.steps, c.B.st, c.s));
+    return download(c.ctx, dist_out, c.res, (uint64_t)c.n, Xfer::Raw64);
 }
 
 }  // namespace
@@ -1119,219 +1407,23 @@ __global__ __launch_bounds__(256) void k_sum_weights(const double *__restrict__ 
 using namespace gx;
 
 extern "C" int gx_sssp(gx_graph *g, uint64_t src, double *dist_out) {
-    if (!g || !dist_out) return fail(GX_NULL_POINTER, "gx_sssp: null argument");
-    if (!g->weighted) return fail(GX_INVALID_VALUE, "gx_sssp: graph has no edge weights");
-    if (src >= g->n) return fail(GX_INVALID_INDEX, "gx_sssp: source out of range");
-    if ((int64_t)g->n >= kMaxBufVertices)
-        return fail(GX_NOT_IMPLEMENTED, "gx_sssp: more than 2^28 vertices (buffer-load offsets are 31-bit)");
-    {
-        gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
-        GX_TRY(hub_for(g, ++g->sssp_calls, &h, &src));
-        if (h) return gx_sssp(h, src, dist_out);
-    }
-    gx_ctx *ctx = g->ctx;
-    GX_HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int64_t n = (int64_t)g->n;
-    const uint64_t qcap = (uint64_t)n + g->nnz / kChunk + 64;
-    // bucket width delta = scale * mean weight / mean degree (GX_SSSP_DELTA overrides); any
-    // positive value gives the same distances, it only trades rounds for re-relaxations
-    if (g->mean_w < 0.0) {
-        double mean = 1.0;
-        if (g->nnz) {
-            DBuf<double> sum;
-            GX_TRY(sum.alloc(1));
-            GX_HIP_TRY(hipMemsetAsync(sum.p, 0, sizeof(double), s));
-            hipLaunchKernelGGL(k_sum_weights, dim3(grid_for(g->nnz, 256, 4096)), dim3(256), 0, s, g->A.w.p,
-                               (int64_t)g->nnz, sum.p);
-            GX_TRY(check_launch("k_sum_weights"));
-            double h = 0.0;
-            GX_HIP_TRY(hipMemcpyAsync(&h, sum.p, sizeof(double), hipMemcpyDeviceToHost, s));
-            GX_HIP_TRY(hipStreamSynchronize(s));
-            mean = h / (double)g->nnz;
-        }
-        g->mean_w = mean;
-    }
-    // measured on the SYN stand-ins with bucket fusion: 2 for undirected graphs,
-    // whose big early buckets are pulled (round 5 re-sweep after the dense opening,
-    // profiles/r05_sssp_dscale_sweep.txt: against 3, SYN-8_5 5.88 -> 5.61 ms, SYN-g500-22
-    // 3.56 -> 3.01, SYN-7_5 1.91 -> 1.80; round 3 had chosen 3 over 4), 0.5 for directed ones
-    double delta = 0.0, scale = g->directed ? 0.5 : 2.0;
-    if (const char *e = std::getenv("GX_SSSP_DELTA")) delta = std::atof(e);
-    if (const char *e = std::getenv("GX_SSSP_DSCALE")) scale = std::atof(e);
-    if (!(delta > 0.0)) {
-        const double avg_deg = g->nnz ? (double)g->nnz / (double)n : 1.0;
-        delta = scale * g->mean_w / std::max(1.0, avg_deg);
-        if (!(delta > 0.0) || !std::isfinite(delta)) delta = 1.0;
-    }
-    const double inv_delta = 1.0 / delta;
-    const bool verbose = std::getenv("GX_SSSP_VERBOSE") != nullptr;
-    DBuf<unsigned long long> stats;
-    if (verbose) {
-        GX_TRY(stats.alloc(8 * kStatLanes));
-        GX_HIP_TRY(hipMemsetAsync(stats.p, 0, 8 * kStatLanes * sizeof(unsigned long long), s));
-    }
-    GX_TRY(device_begin(ctx));
-    {
-        KTimer kt(ctx, "sssp_layout", s);
-        GX_TRY(ensure_sssp_layout(g, delta, s));
-    }
-    SsspLayout &lay = *g->sssp;
-    if (!lay.work) {
-        auto w = std::make_shared<SsspWork>();
-        GX_TRY(w->alloc(n, qcap));
-        lay.work = w;
-    }
-    SsspWork &W = *static_cast<SsspWork *>(lay.work.get());
-    auto &dist = W.dist, &relaxed = W.relaxed;
-    auto &nsw = W.nsw;
-    auto &bstamp = W.bstamp, &ostamp = W.ostamp;
-    auto &st = W.st;
-    SsspBufs B{g->A.rp.p,   lay.lend.p,   lay.ci.p,      lay.w.p,    dist.p,       relaxed.p,  nsw.p,
-               bstamp.p,    ostamp.p,     W.sbits.p,     nbit_words(n), {W.q0.p, W.q1.p}, W.ring.p,
-               {W.ovf0.p, W.ovf1.p},
-               W.settled.p, (uint64_t)n,  delta,         inv_delta,  st.p,         stats.p, 16u};
-    if (const char *e = std::getenv("GX_SSSP_DENSE")) B.dense_div = (uint32_t)std::strtoul(e, nullptr, 10);
-
-    hipLaunchKernelGGL(k_sssp_init, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, dist.p, relaxed.p, nsw.p,
-                       bstamp.p, ostamp.p, n);
-    GX_TRY(check_launch("k_sssp_init"));
-    // heavy phases whose settled list holds at least 1/GX_SSSP_PULL_FRAC (default 8) of the
-    // non-isolated vertices are pulled (undirected graphs; GX_SSSP_PULL=0 never, 2 always).
-    // 8 rather than 4: the same times at the default bucket width, and no cliff below it (a
-    // scale of 2-2.5 left SYN-8_5's first bucket short of 1/4 and pushed it: 14.8 ms; 8.2 at 1/8)
-    uint32_t pull_min = 0xFFFFFFFFu;
-    {
-        const char *e = std::getenv("GX_SSSP_PULL");
-        const int mode = e ? std::atoi(e) : 1;
-        const char *f = std::getenv("GX_SSSP_PULL_FRAC");
-        const double frac = f ? std::atof(f) : 8.0;
-        if (!g->directed && mode == 2) pull_min = 1;
-        else if (!g->directed && mode == 1 && frac > 0.0)
-            pull_min = (uint32_t)std::max<double>(1.0, std::ceil((double)lay.n_active / frac));
-    }
-    // bucket fusion bounds (GX_SSSP_FUSE entries, 0 = one bucket at a time; GX_SSSP_FUSE_MAX
-    // buckets)
-    uint32_t fuse = 0xFFFFFFFFu;
-    int32_t fuse_max = kRing;
-    if (const char *e = std::getenv("GX_SSSP_FUSE")) fuse = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char *e = std::getenv("GX_SSSP_FUSE_MAX")) fuse_max = std::max(1, std::min(kRing, std::atoi(e)));
-    hipLaunchKernelGGL(k_sssp_seed, dim3(1), dim3(256), 0, s, B, (int32_t)src, pull_min, fuse, fuse_max);
-    GX_TRY(check_launch("k_sssp_seed"));
-    const unsigned grid = (unsigned)std::max(1, ctx->num_cus) * 8;
-    // a bound every correct run stays far below: each step settles a vertex or a bucket
-    const uint64_t max_steps = 8ull * (uint64_t)n + 4ull * (uint64_t)g->nnz + 1000000ull;
-    uint64_t steps = 0;
-    int batch = 4;
-    int32_t done = 0;
-    // GX_SSSP_VERBOSE=2: one step per batch, a line per step (bucket, phase, items, work, time)
-    const bool per_step = verbose && std::atoi(std::getenv("GX_SSSP_VERBOSE")) >= 2;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    unsigned long long prev[8] = {};
-    if (per_step) {
-        batch = 1;
-        GX_HIP_TRY(hipEventCreate(&ev0));
-        GX_HIP_TRY(hipEventCreate(&ev1));
-    }
-    const void *res = nullptr;   // the distances to download (set once remapped)
-    const char *ge = std::getenv("GX_SSSP_GRAPH");
-    if (!verbose && !ctx->timing && !(ge && std::atoi(ge) == 0)) {
-        // replayed step graph: one replay always queued behind the one whose done flag is read.
-        // The first batch is as many replays as the last run on this layout needed; when that
-        // was enough, the remap to the caller's order (hub-first copy) is queued behind it
-        // instead of an idle replay, and runs while the host reads the flag.
-        GX_TRY(W.capture(B, grid, s));
-        // capped, so that one long run (a deep chain) cannot queue many idle replays for the next
-        const int hint = std::min(W.replays_hint, 12);
-        auto read_state = [&]() -> int {
-            GX_HIP_TRY(hipMemcpyAsync(W.h_done, &st.p->round, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            GX_HIP_TRY(hipEventRecord(W.ev, s));
-            return GX_SUCCESS;
-        };
-        for (int i = 0; i < std::max(1, hint); i++) GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
-        steps += (uint64_t)std::max(1, hint) * kGraphSteps;
-        GX_TRY(read_state());
-        if (hint > 0) {
-            GX_TRY(remap_out(g, dist.p, 8, s, &res));
-        } else {
-            GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
-            steps += kGraphSteps;
-        }
-        GX_HIP_TRY(hipEventSynchronize(W.ev));
-        if (!W.h_done[1]) res = nullptr;
-        while (!W.h_done[1]) {
-            GX_TRY(read_state());
-            GX_HIP_TRY(hipGraphLaunch(W.gexec, s));
-            GX_HIP_TRY(hipEventSynchronize(W.ev));
-            steps += kGraphSteps;
-            if (steps > max_steps) return fail(GX_PANIC, "gx_sssp: delta-stepping did not converge");
-        }
-        W.replays_hint = (W.h_done[0] + kGraphSteps) / kGraphSteps;   // round + 1 plan steps ran
-        done = 1;
-    }
-    while (!done) {
-        if (per_step) {
-            hipLaunchKernelGGL(k_sssp_plan, dim3(1), dim3(1), 0, s, st.p);
-            SsspState h;
-            GX_HIP_TRY(hipMemcpyAsync(&h, st.p, sizeof(h), hipMemcpyDeviceToHost, s));
-            GX_HIP_TRY(hipEventRecord(ev0, s));
-            hipLaunchKernelGGL(k_sssp_advance, dim3(grid), dim3(kSsspBlock), 0, s, B);
-            hipLaunchKernelGGL(k_sssp_relax, dim3(grid), dim3(kSsspBlock), 0, s, B);
-            GX_HIP_TRY(hipEventRecord(ev1, s));
-            std::vector<unsigned long long> raw(8 * kStatLanes);
-            GX_HIP_TRY(hipMemcpyAsync(raw.data(), stats.p, raw.size() * sizeof(raw[0]), hipMemcpyDeviceToHost, s));
-            GX_HIP_TRY(hipMemcpyAsync(&done, &st.p->done, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            GX_HIP_TRY(hipStreamSynchronize(s));
-            float ms = 0.f;
-            GX_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            unsigned long long c[8] = {};
-            for (int i = 0; i < 8 * kStatLanes; i++) c[i / kStatLanes] += raw[i];
-            std::fprintf(stderr, "step %llu round %d bucket %lld mode %d heavy %d pull %d near %u settled %u | %.1f us "
-                         "items %llu edges %llu improved %llu near %llu ring %llu\n",
-                         (unsigned long long)steps, h.round, (long long)h.cur, h.mode, h.heavy, h.pull,
-                         h.qcnt[h.round & 1], h.settled_cnt, ms * 1e3, c[0] - prev[0], c[1] - prev[1],
-                         c[3] - prev[3], c[4] - prev[4], c[5] - prev[5]);
-            std::memcpy(prev, c, sizeof(c));
-            if (++steps > max_steps) return fail(GX_PANIC, "gx_sssp: delta-stepping did not converge");
-            continue;
-        }
-        for (int i = 0; i < batch; i++) {
-            hipLaunchKernelGGL(k_sssp_plan, dim3(1), dim3(1), 0, s, st.p);
-            {
-                KTimer kt(ctx, "sssp_advance", s);
-                hipLaunchKernelGGL(k_sssp_advance, dim3(grid), dim3(kSsspBlock), 0, s, B);
-            }
-            {
-                KTimer kt(ctx, "sssp_relax", s);
-                hipLaunchKernelGGL(k_sssp_relax, dim3(grid), dim3(kSsspBlock), 0, s, B);
-            }
-        }
-        GX_TRY(check_launch("k_sssp_relax"));
-        steps += batch;
-        GX_HIP_TRY(hipMemcpyAsync(&done, &st.p->done, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        GX_HIP_TRY(hipStreamSynchronize(s));
-        if (steps > max_steps) return fail(GX_PANIC, "gx_sssp: delta-stepping did not converge");
-        batch = std::min(batch * 2, 32);
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (!res) GX_TRY(remap_out(g, dist.p, 8, s, &res));
-    GX_TRY(device_end(ctx));
-    if (verbose) {
-        SsspState h;
-        GX_HIP_TRY(hipMemcpy(&h, st.p, sizeof(h), hipMemcpyDeviceToHost));
-        std::vector<unsigned long long> raw(8 * kStatLanes);
-        GX_HIP_TRY(hipMemcpy(raw.data(), stats.p, raw.size() * sizeof(raw[0]), hipMemcpyDeviceToHost));
-        unsigned long long c[8] = {};
-        for (int i = 0; i < 8 * kStatLanes; i++) c[i / kStatLanes] += raw[i];
-        std::fprintf(stderr,
-                     "gx_sssp: delta %g rounds %d last bucket %lld epochs %d launched steps %llu | items %llu edges "
-                     "%llu tried %llu improved %llu near %llu ring %llu ovf %llu skipped %llu\n",
-                     delta, h.round, (long long)h.cur, h.epoch, (unsigned long long)steps, c[0], c[1], c[2], c[3],
-                     c[4], c[5], c[6], c[7]);
-    }
-    GX_TRY(download(ctx, dist_out, res, (uint64_t)n, Xfer::Raw64));
-    return GX_SUCCESS;
+    GX_TRY(sssp_check_args(g, src, dist_out));
+    gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
+    GX_TRY(hub_for(g, ++g->sssp_calls, &h, &src));
+    if (h) return gx_sssp(h, src, dist_out);
+    GX_HIP_TRY(hipSetDevice(g->ctx->device));
+    SsspCall c(g, src);
+    c.k = sssp_knobs(g->directed, false);       // at every call: tests flip knobs within one process
+    GX_TRY(sssp_graph_stats(g, c.s));
+    c.delta = sssp_delta(g, c.k);
+    GX_TRY(sssp_prepare(c));                    // layout, work buffers
+    c.B = c.W->bufs(g, c.delta, c.cnt.stats.p, c.k.dense_div);
+    GX_TRY(sssp_seed(c));
+    // the replayed step graph unless something has to be read or timed between the steps
+    const auto run = c.k.verbose >= 2 ? run_per_step
+                     : c.k.verbose || c.ctx->timing || !c.k.graph ? run_batched : run_replayed;
+    GX_TRY(run(c));
+    return sssp_finish(c, dist_out);
 }
 
 GX_MODULE_WARMER(sssp)

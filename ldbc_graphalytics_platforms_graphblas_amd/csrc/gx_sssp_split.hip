@@ -11,10 +11,11 @@
 // pulled heavy phase of gx_sssp.hip restated for replicated state):
 //   plan   one thread, from the replicated counts only: LIGHT (relax the frontier queued last
 //          round), HEAVY / PULL (the heavy edges of the vertices settled since the last time:
-//          pushed, or -- undirected, batch >= 1/8 of the vertices with edges -- pulled by the
-//          owned vertices above fl(min settled distance + delta)), ADVANCE (open the next
-//          non-empty slot of the 32-bucket ring, fused with the following ones while they hold
-//          <= n/16 vertices), SPLIT (the overflow into a new ring window) or done;
+//          pushed, or -- a batch of at least pull_min vertices -- pulled by the owned vertices
+//          above fl(min settled distance + delta)), ADVANCE (open the next non-empty slot of
+//          the kRing-bucket ring, fused with the following ones while they hold <= fuse
+//          vertices), SPLIT (the overflow into a new ring window) or done;
+//          delta, pull_min and fuse are gx_sssp.h's rules (sssp_delta, sssp_pull_min, sssp_fuse);
 //   prep   ADVANCE: the opened slots' pending vertices -> this round's frontier; SPLIT: the
 //          overflow -> ring / new overflow; HEAVY / PULL: the batch marked (PULL: its minimum);
 //   relax  up to 64 (vertex, 256-edge chunk) items of this rank's slice per wave; PULL: the
@@ -27,22 +28,18 @@
 // Distances are the relaxation fixed point, bitwise the oracle's and gx_sssp's whatever the
 // split or delta (gx_sssp.hip header).
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 
 #include <rocprim/rocprim.hpp>
 
-#include "gx_device.h"
+#include "gx_sssp.h"
 
 namespace gx {
 namespace {
 
 constexpr int kSB = 256;        // threads per block
-constexpr int kSChunk = 256;    // edges per relax item
-constexpr int kW = 32;          // bucket ring slots
 constexpr int kSmallDeg = 32;   // PULL: candidates up to this many heavy in-edges take a thread
 constexpr int kBigCap = 1024;   // PULL: larger candidates listed per workgroup for its waves
 constexpr unsigned long long kInf = 0x7FF0000000000000ull;   // +inf bits
@@ -53,7 +50,7 @@ enum : int32_t { kNone = 0, kLight = 1, kHeavy = 2, kAdvance = 3, kPull = 4, kSp
 // counters (which differ by rank and never enter a decision).
 struct SplitState {
     int64_t cur;                  // last bucket of the group being settled
-    int64_t win_base;             // ring window [win_base, win_base + kW)
+    int64_t win_base;             // ring window [win_base, win_base + kRing)
     unsigned long long ovf_minb;  // smallest bucket on the overflow list being filled
     unsigned long long smin;      // PULL: smallest distance of the settled batch
     int32_t mode, round, epoch, done;
@@ -68,7 +65,7 @@ struct SplitState {
     uint32_t si, si_done;         // their heavy items (rank-local) / relaxed so far
     uint32_t hs0, hs1;            // HEAVY: items [hs0, hs1); HEAVY / PULL: vertices [sb0, sb1)
     uint32_t sb0, sb1;
-    uint32_t ring_cnt[kW];
+    uint32_t ring_cnt[kRing];
     uint32_t ovf_cnt[2];
     uint32_t nimp;                // improved owned vertices this round (rank-local)
     uint32_t pull_min;            // settled batch size from which the heavy phase is pulled (0: never)
@@ -116,20 +113,13 @@ struct SplitBufs {
     uint64_t *fitems[2];          // (u << 32 | chunk)
     uint64_t *sitems;             // heavy items of the settled vertices
     int32_t *sverts;              // settled vertices of the epoch (replicated set)
-    int32_t *ring;                // kW slots of n vertices
+    int32_t *ring;                // kRing slots of n vertices
     int32_t *ovf[2];
     int32_t *imp;                 // improved owned vertices (global ids)
     int64_t n, v0, v1;
     double delta, inv_delta;
     SplitState *st;
 };
-
-__device__ __forceinline__ int64_t sbucket(unsigned long long bits, double inv_delta) {
-    const double q = __longlong_as_double((long long)bits) * inv_delta;
-    return q < 4.0e18 ? (int64_t)q : (int64_t)4000000000000000000ll;
-}
-
-__device__ __forceinline__ uint32_t nchunks(int64_t len) { return (uint32_t)max<int64_t>(1, (len + kSChunk - 1) / kSChunk); }
 
 // ---- tile reservations ----
 // A kernel that queues vertices works in tiles of kSB * kPer elements per workgroup: each element
@@ -138,7 +128,7 @@ __device__ __forceinline__ uint32_t nchunks(int64_t len) { return (uint32_t)max<
 // tile instead of one per wave (same-address atomics serialise at ~11-20 ns each: the first
 // version of this file spent most of its time there).
 constexpr int kPer = 8;                    // elements per thread and tile
-enum : int { kQFv = 0, kQFi, kQSv, kQSi, kQOvf, kQRing, kQCat = kQRing + kW };
+enum : int { kQFv = 0, kQFi, kQSv, kQSi, kQOvf, kQRing, kQCat = kQRing + kRing };
 
 // elements per thread for `tot` elements over the grid: the full kPer only when the input
 // fills every workgroup's tiles (a small input on few workgroups would run kPer dependent
@@ -183,24 +173,24 @@ __device__ __forceinline__ void tile_stage(const SplitBufs &B, Tile &T, Push &P,
     if (take) {
         B.lrel[v] = d;
         const VRec vr = B.vrec[v];
-        P.nl = nchunks(vr.nl);
+        P.nl = chunks_min1(vr.nl);
         atomicAdd(&T.cnt[kQFv], 1u);
         P.offi = atomicAdd(&T.cnt[kQFi], P.nl);
         if (r.sstamp != epoch || r.hmark >= st->epoch_round) {
             B.srec[v].sstamp = epoch;
             B.srec[v].hmark = 0;
             P.isv = 1;
-            P.nh = nchunks(vr.nh);
+            P.nh = chunks_min1(vr.nh);
             P.offsv = atomicAdd(&T.cnt[kQSv], 1u);
             P.offs = atomicAdd(&T.cnt[kQSi], P.nh);
         }
     }
     if (far) {
-        if (b < st->win_base + kW) {
+        if (b < st->win_base + kRing) {
             const int32_t btag = (int32_t)(uint32_t)b + 1;
             if (r.bstamp != btag) {
                 B.srec[v].bstamp = btag;
-                P.q = (int8_t)(kQRing + (int)(b % kW));
+                P.q = (int8_t)(kQRing + (int)(b % kRing));
                 P.offr = atomicAdd(&T.cnt[P.q], 1u);
             }
         } else {
@@ -308,7 +298,7 @@ __device__ void k_split_plan_body(SplitState *st) {
         return;
     }
     if (st->consume >= 0) {
-        for (int j = 0; j < st->consume_n; j++) st->ring_cnt[(st->consume + j) % kW] = 0;
+        for (int j = 0; j < st->consume_n; j++) st->ring_cnt[(st->consume + j) % kRing] = 0;
         st->consume = -1;
     }
     const int nx = st->fc ^ 1;
@@ -337,21 +327,21 @@ __device__ void k_split_plan_body(SplitState *st) {
     }
     // open the next non-empty ring bucket, with the following ones while the vertices stay
     // within `fuse` (bucket fusion; any grouping reaches the same fixed point)
-    const int64_t lim = st->win_base + kW;
+    const int64_t lim = st->win_base + kRing;
     for (int64_t b = st->cur + 1; b < lim; b++) {
-        const uint32_t c0 = st->ring_cnt[b % kW];
+        const uint32_t c0 = st->ring_cnt[b % kRing];
         if (c0 == 0) continue;
         uint32_t tot = c0;
         int64_t last = b;
         for (int64_t b2 = b + 1; b2 < lim; b2++) {
-            const uint32_t c = st->ring_cnt[b2 % kW];
+            const uint32_t c = st->ring_cnt[b2 % kRing];
             if (tot + c > st->fuse) break;
             tot += c;
             last = b2;
         }
         st->mode = kAdvance;
         st->cur = last;
-        st->slot0 = (int32_t)(b % kW);
+        st->slot0 = (int32_t)(b % kRing);
         st->nslots = (int32_t)(last - b + 1);
         st->consume = st->slot0;
         st->consume_n = st->nslots;
@@ -365,7 +355,7 @@ __device__ void k_split_plan_body(SplitState *st) {
     }
     const int src = st->oe;
     if (st->ovf_cnt[src] > 0) {   // new ring window from the overflow
-        const int64_t mb = (int64_t)min(st->ovf_minb, 4000000000000000000ull);
+        const int64_t mb = (int64_t)min(st->ovf_minb, (unsigned long long)kMaxBucket);
         st->win_base = max(st->cur + 1, mb);
         st->cur = st->win_base - 1;
         st->oe = src ^ 1;
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(kSB) void k_split_prep(SplitBufs B) {
         const int32_t round = st->round, epoch = st->epoch, fc = st->fc;
         // the opened slots' entries as one index space
         uint32_t tot = 0;
-        for (int j = 0; j < st->nslots; j++) tot += st->ring_cnt[(st->slot0 + j) % kW];
+        for (int j = 0; j < st->nslots; j++) tot += st->ring_cnt[(st->slot0 + j) % kRing];
         const uint32_t per = tile_per(tot), tile = per * kSB;
         for (uint32_t t0 = blockIdx.x * tile; t0 < tot; t0 += gridDim.x * tile) {
             tile_begin(T);
@@ -405,16 +395,16 @@ __global__ __launch_bounds__(kSB) void k_split_prep(SplitBufs B) {
                 int32_t v = 0;
                 if (valid) {
                     int j = 0;
-                    uint32_t c = st->ring_cnt[st->slot0 % kW];
+                    uint32_t c = st->ring_cnt[st->slot0 % kRing];
                     while (i >= c) {
                         i -= c;
                         j++;
-                        c = st->ring_cnt[(st->slot0 + j) % kW];
+                        c = st->ring_cnt[(st->slot0 + j) % kRing];
                     }
-                    v = B.ring[(uint64_t)((st->slot0 + j) % kW) * (uint64_t)B.n + i];
+                    v = B.ring[(uint64_t)((st->slot0 + j) % kRing) * (uint64_t)B.n + i];
                 }
                 const unsigned long long d = valid ? B.dist[v] : kInf;
-                bool now = valid && d < B.lrel[v] && sbucket(d, B.inv_delta) <= cur;
+                bool now = valid && d < B.lrel[v] && bucket_of(bitsd(d), B.inv_delta) <= cur;
                 if (now) now = B.qstamp[v] != round && atomicExch(&B.qstamp[v], round) != round;
                 tile_stage(B, T, P[k], now, false, v, d, 0, epoch);
             }
@@ -437,7 +427,7 @@ __global__ __launch_bounds__(kSB) void k_split_prep(SplitBufs B) {
                 const int32_t v = valid ? B.ovf[src][i] : 0;
                 const unsigned long long d = valid ? B.dist[v] : kInf;
                 const bool pend = valid && d < B.lrel[v];
-                tile_stage(B, T, P[k], false, pend, v, d, pend ? sbucket(d, B.inv_delta) : 0, 0);
+                tile_stage(B, T, P[k], false, pend, v, d, pend ? bucket_of(bitsd(d), B.inv_delta) : 0, 0);
             }
             tile_reserve(st, T, 0);
 #pragma unroll
@@ -497,15 +487,13 @@ __global__ __launch_bounds__(kSB) void k_split_relax(SplitBufs B) {
         __shared__ uint32_t nbig;
         if (threadIdx.x == 0) nbig = 0;
         __syncthreads();
-        const unsigned long long lim =
-            (unsigned long long)__double_as_longlong(__longlong_as_double((long long)st->smin) + B.delta);
+        const unsigned long long lim = dbits(bitsd(st->smin) + B.delta);
         auto pull_row = [&](int64_t i) {
             unsigned long long best = kInf;
             for (int64_t e = B.orp[i]; e < B.orp[i + 1]; e++) {
                 const int32_t u = B.oci[e];
                 if (B.srec[u].hmark == round) {
-                    const unsigned long long nd =
-                        (unsigned long long)__double_as_longlong(__longlong_as_double((long long)B.dist[u]) + B.ow[e]);
+                    const unsigned long long nd = dbits(bitsd(B.dist[u]) + B.ow[e]);
                     best = min(best, nd);
                 }
             }
@@ -543,8 +531,7 @@ __global__ __launch_bounds__(kSB) void k_split_relax(SplitBufs B) {
             for (int64_t e = B.orp[i] + lane; e < B.orp[i + 1]; e += kWave) {
                 const int32_t u = B.oci[e];
                 if (B.srec[u].hmark == round) {
-                    const unsigned long long nd =
-                        (unsigned long long)__double_as_longlong(__longlong_as_double((long long)B.dist[u]) + B.ow[e]);
+                    const unsigned long long nd = dbits(bitsd(B.dist[u]) + B.ow[e]);
                     best = min(best, nd);
                 }
             }
@@ -573,8 +560,8 @@ __global__ __launch_bounds__(kSB) void k_split_relax(SplitBufs B) {
                 const int64_t u = (int64_t)(x >> 32), j = (int64_t)(x & 0xffffffffu);
                 const VRec vr = B.vrec[u];
                 const int64_t a = heavy ? vr.start + vr.nl : vr.start, b = a + (heavy ? vr.nh : vr.nl);
-                e0 = a + j * kSChunk;
-                len = max<int64_t>(0, min(b, e0 + kSChunk) - e0);
+                e0 = a + j * kChunk;
+                len = max<int64_t>(0, min(b, e0 + kChunk) - e0);
                 du = B.dist[u];
             }
             // exclusive prefix of the items' lengths (<= 64 x 256: 32 bits)
@@ -607,14 +594,14 @@ __global__ __launch_bounds__(kSB) void k_split_relax(SplitBufs B) {
                     }
                     const int64_t eo = __shfl(e0, lo, kWave);
                     const uint32_t po = __shfl(pre, lo, kWave);
-                    const unsigned long long dbits = __shfl(du, lo, kWave);
+                    const unsigned long long dsrc = __shfl(du, lo, kWave);
                     live[q] = k < total;
                     t[q] = 0;
                     nd[q] = kInf;
                     if (live[q]) {
                         const int64_t e = eo + (int64_t)(k - po);
                         t[q] = B.sci[e];
-                        nd[q] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)dbits) + B.sw[e]);
+                        nd[q] = dbits(bitsd(dsrc) + B.sw[e]);
                     }
                 }
                 unsigned long long cur[kQ];
@@ -697,7 +684,7 @@ __global__ __launch_bounds__(kSB) void k_split_apply(SplitBufs B, const uint64_t
                 d = pr[1];
                 if (d < B.dist[v]) B.dist[v] = d;   // one pair per vertex and round
             }
-            const int64_t b = valid ? sbucket(d, B.inv_delta) : 0;
+            const int64_t b = valid ? bucket_of(bitsd(d), B.inv_delta) : 0;
             const bool near = valid && b <= cur;
             tile_stage(B, T, P[k], near, valid && !near, v, d, b, epoch);
         }
@@ -814,23 +801,6 @@ __global__ __launch_bounds__(kSB) void k_own_scatter(const int64_t *__restrict__
     }
 }
 
-// Per-block partial sums of the weights in a fixed order (grid-stride per thread, butterfly per
-// wave, waves in index order), so the bucket width derived from them is bitwise the same on
-// every rank that holds the same graph: the ranks' scheduling decisions must agree.
-__global__ __launch_bounds__(256) void k_split_sum_w(const double *__restrict__ w, int64_t m, double *part) {
-    __shared__ double wsum[256 / kWave];
-    double acc = 0.0;
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < m; k += (int64_t)gridDim.x * 256) acc += w[k];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 256 / kWave; i++) t += wsum[i];
-        part[blockIdx.x] = t;
-    }
-}
-
 }  // namespace
 }  // namespace gx
 
@@ -891,10 +861,6 @@ struct gx_sssp_split {
     }
 };
 
-// as the other *_part_* steps (gx.h): NULL is the null (default) stream -- torch's -- so the
-// steps order with the tensors and collectives issued there
-static hipStream_t split_stream(gx_sssp_split *, void *stream) { return (hipStream_t)stream; }
-
 // plan -> prep -> relax -> pairs (this rank's improved owned vertices; a single rank's device
 // loop skips the pairs: its apply reads the improved list)
 static int split_relax(gx_sssp_split *p, uint64_t *pairs, uint64_t *count, hipStream_t s) {
@@ -918,7 +884,7 @@ extern "C" int gx_sssp_split_create(gx_graph *g, uint64_t v0, uint64_t v1, gx_ss
     if (!g || !out) return fail(GX_NULL_POINTER, "gx_sssp_split_create: null argument");
     if (!g->weighted) return fail(GX_INVALID_VALUE, "gx_sssp_split_create: graph has no edge weights");
     if (v0 > v1 || v1 > g->n) return fail(GX_INVALID_INDEX, "gx_sssp_split_create: bad vertex range");
-    if (g->n >= (1ull << 31) / kW) return fail(GX_NOT_IMPLEMENTED, "gx_sssp_split_create: more than 2^26 vertices");
+    if (g->n >= (1ull << 31) / kRing) return fail(GX_NOT_IMPLEMENTED, "gx_sssp_split_create: more than 2^26 vertices");
     GX_HIP_TRY(hipSetDevice(g->ctx->device));
     std::unique_ptr<gx_sssp_split> p(new gx_sssp_split());
     p->caller = g;
@@ -929,111 +895,79 @@ extern "C" int gx_sssp_split_create(gx_graph *g, uint64_t v0, uint64_t v1, gx_ss
     return GX_SUCCESS;
 }
 
-// The slice, the PULL layout and the work buffers of p for graph g (the caller's graph, or
-// for gx_sssp_split_run its hub-first copy); earlier buffers are released.
-static int split_build(gx_sssp_split *p, gx_graph *g) {
-    hipStream_t s = g->ctx->stream;
-    p->g = g;
-    p->n = (int64_t)g->n;
-    const int64_t n = p->n, own = p->v1 - p->v0;
-    // bucket width: gx_sssp's rule (scale x mean weight / mean degree; GX_SSSP_DELTA and
-    // GX_SSSP_DSCALE override) -- any positive value gives the same distances
-    double mean = 1.0;
-    if (g->nnz) {
-        const unsigned sgrid = grid_for(g->nnz, 256, 4096);
-        DBuf<double> part;
-        GX_TRY(part.alloc(sgrid));
-        hipLaunchKernelGGL(k_split_sum_w, dim3(sgrid), dim3(256), 0, s, g->A.w.p, (int64_t)g->nnz, part.p);
-        GX_TRY(check_launch("k_split_sum_w"));
-        std::vector<double> h(sgrid);
-        GX_HIP_TRY(hipMemcpyAsync(h.data(), part.p, sgrid * sizeof(double), hipMemcpyDeviceToHost, s));
-        GX_HIP_TRY(hipStreamSynchronize(s));
-        double t = 0.0;
-        for (double x : h) t += x;   // block order: deterministic for a given graph
-        mean = t / (double)g->nnz;
-    }
-    double scale = g->directed ? 0.5 : 3.0, delta = 0.0;   // SYN-8_5 N = 1: 9.3-9.4 ms at 3, 9.7 at 4
-    if (const char *e = std::getenv("GX_SSSP_DSCALE")) scale = std::atof(e);
-    if (const char *e = std::getenv("GX_SSSP_DELTA")) delta = std::atof(e);
-    if (!(delta > 0.0)) delta = scale * mean / std::max(1.0, (double)g->nnz / std::max<double>(1.0, (double)n));
-    if (!(delta > 0.0) || !std::isfinite(delta)) delta = 1.0;
-    p->delta = delta;
-    // the heavy phase is pulled (undirected graphs) once the settled batch holds 1/8 of the
-    // vertices with edges (gx_sssp's rule; GX_SSSP_PULL = 0 never, 2 always); buckets are fused
-    // while they hold at most n / 16 vertices (GX_SSSP_FUSE)
-    int64_t nonisolated = n;
-    GX_TRY(ensure_host_rp(g->ctx, g->A));
-    if ((int64_t)g->A.h_rp.size() == n + 1) {
-        nonisolated = 0;
-        for (int64_t v = 0; v < n; v++) nonisolated += g->A.h_rp[v + 1] != g->A.h_rp[v];
-    }
-    const int pull_mode = std::getenv("GX_SSSP_PULL") ? std::atoi(std::getenv("GX_SSSP_PULL")) : 1;
-    const bool can_pull = !g->directed && pull_mode != 0;
-    p->pull_min = !can_pull ? 0u : pull_mode == 2 ? 1u : (uint32_t)std::max<int64_t>(1, nonisolated / 8);
-    p->fuse = std::getenv("GX_SSSP_FUSE") ? (uint32_t)std::max(1, std::atoi(std::getenv("GX_SSSP_FUSE")))
-                                          : (uint32_t)std::max<int64_t>(1024, n / 16);
-    const unsigned wg_all = grid_for((uint64_t)std::max<int64_t>(n, 1) * kWave, kSB, 16384);
-    // slice: count, scan, scatter
-    GX_TRY(p->vrec.alloc(std::max<int64_t>(n, 1)));
-    {
-        DBuf<int64_t> lc, tc, srp, slend;
-        GX_TRY(srp.alloc(n + 1));
-        GX_TRY(slend.alloc(std::max<int64_t>(n, 1)));
-        GX_TRY(lc.alloc(std::max<int64_t>(n, 1)));
-        GX_TRY(tc.alloc(n + 1));
-        if (n) {
-            hipLaunchKernelGGL(k_slice_count, dim3(wg_all), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, n, p->v0,
-                               p->v1, delta, lc.p, tc.p);
-            GX_TRY(check_launch("k_slice_count"));
-        } else {
-            GX_HIP_TRY(hipMemsetAsync(tc.p, 0, sizeof(int64_t), s));
-        }
-        GX_TRY(scan_exclusive_i64(tc.p, srp.p, (size_t)(n + 1), s));
-        GX_HIP_TRY(hipMemcpyAsync(&p->snnz, srp.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        GX_HIP_TRY(hipStreamSynchronize(s));
-        GX_TRY(p->sci.alloc(std::max<int64_t>(p->snnz, 1)));
-        GX_TRY(p->sw.alloc(std::max<int64_t>(p->snnz, 1)));
-        if (n) {
-            hipLaunchKernelGGL(k_slice_scatter, dim3(wg_all), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, n, p->v0,
-                               p->v1, delta, srp.p, lc.p, slend.p, p->sci.p, p->sw.p);
-            GX_TRY(check_launch("k_slice_scatter"));
-            hipLaunchKernelGGL(k_slice_vrec, dim3(grid_for(n, kSB, 8192)), dim3(kSB), 0, s, srp.p, slend.p, n, p->vrec.p);
-            GX_TRY(check_launch("k_slice_vrec"));
-        }
-        GX_HIP_TRY(hipStreamSynchronize(s));   // lc / tc die here
-    }
-    // owned rows' heavy in-edges (PULL)
-    GX_TRY(p->orp.alloc(own + 1));
-    if (can_pull) {
-        DBuf<int64_t> cnt;
-        GX_TRY(cnt.alloc(own + 1));
-        const unsigned wg_own = grid_for((uint64_t)std::max<int64_t>(own, 1) * kWave, kSB, 16384);
-        hipLaunchKernelGGL(k_own_count, dim3(wg_own), dim3(kSB), 0, s, g->A.rp.p, g->A.w.p, p->v0, p->v1, delta, cnt.p);
-        GX_TRY(check_launch("k_own_count"));
-        GX_TRY(scan_exclusive_i64(cnt.p, p->orp.p, (size_t)(own + 1), s));
-        GX_HIP_TRY(hipMemcpyAsync(&p->onnz, p->orp.p + own, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        GX_HIP_TRY(hipStreamSynchronize(s));
-        GX_TRY(p->oci.alloc(std::max<int64_t>(p->onnz, 1)));
-        GX_TRY(p->ow.alloc(std::max<int64_t>(p->onnz, 1)));
-        if (own) {
-            hipLaunchKernelGGL(k_own_scatter, dim3(wg_own), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, p->v0, p->v1,
-                               delta, p->orp.p, p->oci.p, p->ow.p);
-            GX_TRY(check_launch("k_own_scatter"));
-        }
-        GX_HIP_TRY(hipStreamSynchronize(s));
+static int64_t at_least_1(int64_t x) { return std::max<int64_t>(x, 1); }
+
+// The slice: the entries of g whose target is owned, by source, light first (count, scan, scatter).
+static int split_slice(gx_sssp_split *p, gx_graph *g, hipStream_t s) {
+    const int64_t n = p->n;
+    const unsigned wg_all = grid_for((uint64_t)at_least_1(n) * kWave, kSB, 16384);
+    GX_TRY(p->vrec.alloc(at_least_1(n)));
+    DBuf<int64_t> lc, tc, srp, slend;
+    GX_TRY(srp.alloc(n + 1));
+    GX_TRY(slend.alloc(at_least_1(n)));
+    GX_TRY(lc.alloc(at_least_1(n)));
+    GX_TRY(tc.alloc(n + 1));
+    if (n) {
+        hipLaunchKernelGGL(k_slice_count, dim3(wg_all), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, n, p->v0, p->v1,
+                           p->delta, lc.p, tc.p);
+        GX_TRY(check_launch("k_slice_count"));
     } else {
-        GX_HIP_TRY(hipMemset(p->orp.p, 0, (own + 1) * sizeof(int64_t)));
+        GX_HIP_TRY(hipMemsetAsync(tc.p, 0, sizeof(int64_t), s));
     }
-    // state: item lists hold at most one item per vertex plus one per 256 slice entries
-    const uint64_t icap = (uint64_t)n + (uint64_t)p->snnz / kSChunk + 64;
-    const int64_t n1 = std::max<int64_t>(n, 1), own1 = std::max<int64_t>(own, 1);
+    GX_TRY(scan_exclusive_i64(tc.p, srp.p, (size_t)(n + 1), s));
+    GX_HIP_TRY(hipMemcpyAsync(&p->snnz, srp.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GX_HIP_TRY(hipStreamSynchronize(s));
+    GX_TRY(p->sci.alloc(at_least_1(p->snnz)));
+    GX_TRY(p->sw.alloc(at_least_1(p->snnz)));
+    if (n) {
+        hipLaunchKernelGGL(k_slice_scatter, dim3(wg_all), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, n, p->v0,
+                           p->v1, p->delta, srp.p, lc.p, slend.p, p->sci.p, p->sw.p);
+        GX_TRY(check_launch("k_slice_scatter"));
+        hipLaunchKernelGGL(k_slice_vrec, dim3(grid_for(n, kSB, 8192)), dim3(kSB), 0, s, srp.p, slend.p, n, p->vrec.p);
+        GX_TRY(check_launch("k_slice_vrec"));
+    }
+    GX_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
+    return GX_SUCCESS;
+}
+
+// The owned rows' heavy in-edges, for PULL (none when the heavy phase is never pulled).
+static int split_owned_heavy(gx_sssp_split *p, gx_graph *g, hipStream_t s) {
+    const int64_t own = p->v1 - p->v0;
+    GX_TRY(p->orp.alloc(own + 1));
+    if (p->pull_min == 0) {
+        GX_HIP_TRY(hipMemset(p->orp.p, 0, (own + 1) * sizeof(int64_t)));
+        return GX_SUCCESS;
+    }
+    DBuf<int64_t> cnt;
+    GX_TRY(cnt.alloc(own + 1));
+    const unsigned wg_own = grid_for((uint64_t)at_least_1(own) * kWave, kSB, 16384);
+    hipLaunchKernelGGL(k_own_count, dim3(wg_own), dim3(kSB), 0, s, g->A.rp.p, g->A.w.p, p->v0, p->v1, p->delta, cnt.p);
+    GX_TRY(check_launch("k_own_count"));
+    GX_TRY(scan_exclusive_i64(cnt.p, p->orp.p, (size_t)(own + 1), s));
+    GX_HIP_TRY(hipMemcpyAsync(&p->onnz, p->orp.p + own, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GX_HIP_TRY(hipStreamSynchronize(s));
+    GX_TRY(p->oci.alloc(at_least_1(p->onnz)));
+    GX_TRY(p->ow.alloc(at_least_1(p->onnz)));
+    if (own) {
+        hipLaunchKernelGGL(k_own_scatter, dim3(wg_own), dim3(kSB), 0, s, g->A.rp.p, g->A.ci.p, g->A.w.p, p->v0, p->v1,
+                           p->delta, p->orp.p, p->oci.p, p->ow.p);
+        GX_TRY(check_launch("k_own_scatter"));
+    }
+    GX_HIP_TRY(hipStreamSynchronize(s));
+    return GX_SUCCESS;
+}
+
+// The state buffers: item lists hold at most one item per vertex plus one per 256 slice entries.
+static int split_state(gx_sssp_split *p, gx_graph *g) {
+    const uint64_t icap = (uint64_t)p->n + (uint64_t)p->snnz / kChunk + 64;
+    const int64_t n1 = at_least_1(p->n), own1 = at_least_1(p->v1 - p->v0);
     p->sv_cap = (uint32_t)n1;
     p->si_cap = icap;
     GX_TRY(p->dist.alloc(n1));
     GX_TRY(p->lrel.alloc(n1));
     for (DBuf<int32_t> *b : {&p->qstamp, &p->sverts, &p->ovf0, &p->ovf1}) GX_TRY(b->alloc(n1));
     GX_TRY(p->srec.alloc(n1));
-    GX_TRY(p->ring.alloc((uint64_t)n1 * kW));
+    GX_TRY(p->ring.alloc((uint64_t)n1 * kRing));
     GX_TRY(p->istamp.alloc(own1));
     GX_TRY(p->imp.alloc(own1));
     GX_TRY(p->fitems0.alloc(icap));
@@ -1046,6 +980,23 @@ static int split_build(gx_sssp_split *p, gx_graph *g) {
         GX_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p->h_done), 2 * sizeof(int32_t), hipHostMallocDefault));
     p->grid = (unsigned)std::max(1, g->ctx->num_cus) * 8;
     return GX_SUCCESS;
+}
+
+// The slice, the PULL layout and the work buffers of p for graph g (the caller's graph, or
+// for gx_sssp_split_run its hub-first copy); earlier buffers are released.  The bucket width,
+// the pull threshold and the fusion bound are gx_sssp.h's rules with the split's defaults.
+static int split_build(gx_sssp_split *p, gx_graph *g) {
+    hipStream_t s = g->ctx->stream;
+    p->g = g;
+    p->n = (int64_t)g->n;
+    const SsspKnobs k = sssp_knobs(g->directed, true);
+    GX_TRY(sssp_graph_stats(g, s));
+    p->delta = sssp_delta(g, k);
+    p->pull_min = sssp_pull_min(g, k);
+    p->fuse = sssp_fuse(g, k);
+    GX_TRY(split_slice(p, g, s));
+    GX_TRY(split_owned_heavy(p, g, s));
+    return split_state(p, g);
 }
 
 extern "C" int gx_sssp_split_free(gx_sssp_split *p) {
@@ -1062,15 +1013,16 @@ extern "C" int gx_sssp_split_delta(gx_sssp_split *p, double *delta) {
     return GX_SUCCESS;
 }
 
+// `stream` of the per-rank steps, as the other *_part_* steps (gx.h): NULL is the null (default)
+// stream -- torch's -- so the steps order with the tensors and collectives issued there.
 extern "C" int gx_sssp_split_start(gx_sssp_split *p, uint64_t src, void *stream) {
     if (!p) return fail(GX_NULL_POINTER, "gx_sssp_split_start: null argument");
     if (src >= (uint64_t)p->n) return fail(GX_INVALID_INDEX, "gx_sssp_split_start: source out of range");
     if (p->g != p->caller) src = (uint64_t)p->caller->h_hub_perm[src];
     GX_HIP_TRY(hipSetDevice(p->g->ctx->device));
-    hipStream_t s = split_stream(p, stream);
+    hipStream_t s = (hipStream_t)stream;
     const SplitBufs B = p->bufs();
-    hipLaunchKernelGGL(k_split_start, dim3(grid_for(std::max<int64_t>(p->n, 1), kSB, 8192)), dim3(kSB), 0, s, B,
-                       (int64_t)src);
+    hipLaunchKernelGGL(k_split_start, dim3(grid_for(at_least_1(p->n), kSB, 8192)), dim3(kSB), 0, s, B, (int64_t)src);
     hipLaunchKernelGGL(k_split_seed, dim3(1), dim3(kSB), 0, s, B, (int64_t)src, p->pull_min, p->fuse, p->sv_cap,
                        p->si_cap);
     return check_launch("k_split_seed");
@@ -1079,7 +1031,7 @@ extern "C" int gx_sssp_split_start(gx_sssp_split *p, uint64_t src, void *stream)
 extern "C" int gx_sssp_split_relax(gx_sssp_split *p, uint64_t *pairs, uint64_t *count, void *stream) {
     if (!p || !pairs || !count) return fail(GX_NULL_POINTER, "gx_sssp_split_relax: null argument");
     GX_HIP_TRY(hipSetDevice(p->g->ctx->device));
-    return split_relax(p, pairs, count, split_stream(p, stream));
+    return split_relax(p, pairs, count, (hipStream_t)stream);
 }
 
 extern "C" int gx_sssp_split_apply(gx_sssp_split *p, const uint64_t *pairs, const uint64_t *counts, int nranks,
@@ -1087,7 +1039,7 @@ extern "C" int gx_sssp_split_apply(gx_sssp_split *p, const uint64_t *pairs, cons
     if (!p || !counts || (nranks > 0 && !pairs && stride)) return fail(GX_NULL_POINTER, "gx_sssp_split_apply: null argument");
     if (nranks < 1) return fail(GX_INVALID_VALUE, "gx_sssp_split_apply: nranks < 1");
     GX_HIP_TRY(hipSetDevice(p->g->ctx->device));
-    return split_apply(p, pairs, counts, nranks, stride, split_stream(p, stream));
+    return split_apply(p, pairs, counts, nranks, stride, (hipStream_t)stream);
 }
 
 // Fails when the run stopped on a full settled list (SplitState::err) instead of finishing.
@@ -1102,11 +1054,27 @@ int gx::sssp_split_check(gx_sssp_split *p, hipStream_t s) {
 extern "C" int gx_sssp_split_distances(gx_sssp_split *p, double *dist, void *stream) {
     if (!p || !dist) return fail(GX_NULL_POINTER, "gx_sssp_split_distances: null argument");
     GX_HIP_TRY(hipSetDevice(p->g->ctx->device));
-    hipStream_t s = split_stream(p, stream);
+    hipStream_t s = (hipStream_t)stream;
     GX_TRY(sssp_split_check(p, s));
     const void *res = nullptr;
     GX_TRY(remap_out(p->g, p->dist.p, 8, s, &res));   // hub-first copy -> the caller's order
     GX_HIP_TRY(hipMemcpyAsync(dist, res, (size_t)p->n * 8, hipMemcpyDeviceToDevice, s));
+    return GX_SUCCESS;
+}
+
+// GX_SPLIT_VERBOSE: the finished run's rounds per mode and the mode of its first 256 rounds.
+static int split_report(gx_sssp_split *p) {
+    if (!sssp_knobs(p->g->directed, true).split_verbose) return GX_SUCCESS;
+    SplitState h;
+    GX_HIP_TRY(hipMemcpy(&h, p->st.p, sizeof(h), hipMemcpyDeviceToHost));
+    std::fprintf(stderr,
+                 "[gx_sssp_split] delta %.4g rounds %d: light %u (items %llu), heavy push %u (items %llu), "
+                 "pull %u, advance %u, split %u\n",
+                 p->delta, h.round, h.nmode[kLight], h.nitems[kLight], h.nmode[kHeavy], h.nitems[kHeavy],
+                 h.nmode[kPull], h.nmode[kAdvance], h.nmode[kSplit]);
+    std::fprintf(stderr, "[gx_sssp_split] modes:");
+    for (int i = 0; i < std::min(h.round, 256); i++) std::fprintf(stderr, " %d", (int)h.modelog[i]);
+    std::fprintf(stderr, "\n");
     return GX_SUCCESS;
 }
 
@@ -1148,18 +1116,7 @@ extern "C" int gx_sssp_split_run(gx_sssp_split *p, uint64_t src, double *dist_ho
         p->rounds_hint = rounds;
     }
     GX_TRY(device_end(ctx));
-    if (std::getenv("GX_SPLIT_VERBOSE")) {
-        SplitState h;
-        GX_HIP_TRY(hipMemcpy(&h, p->st.p, sizeof(h), hipMemcpyDeviceToHost));
-        std::fprintf(stderr,
-                     "[gx_sssp_split] delta %.4g rounds %d: light %u (items %llu), heavy push %u (items %llu), "
-                     "pull %u, advance %u, split %u\n",
-                     p->delta, h.round, h.nmode[kLight], h.nitems[kLight], h.nmode[kHeavy], h.nitems[kHeavy],
-                     h.nmode[kPull], h.nmode[kAdvance], h.nmode[kSplit]);
-        std::fprintf(stderr, "[gx_sssp_split] modes:");
-        for (int i = 0; i < std::min(h.round, 256); i++) std::fprintf(stderr, " %d", (int)h.modelog[i]);
-        std::fprintf(stderr, "\n");
-    }
+    GX_TRY(split_report(p));
     GX_TRY(sssp_split_check(p, s));
     const void *res = nullptr;
     GX_TRY(remap_out(p->g, p->dist.p, 8, s, &res));   // hub-first copy -> the caller's order

@@ -350,6 +350,34 @@ def test_sssp_repeated_runs_reuse_work_buffers(ctx, monkeypatch, graph_replay):
         G.close()
 
 
+@pytest.mark.parametrize("level", ["1", "2"])
+def test_sssp_verbose_runs(ctx, monkeypatch, capfd, level):
+    """GX_SSSP_VERBOSE=1 (batched steps, a summary line) and =2 (one step at a time, a line per
+    step): two sources on one resident graph (the second call runs on the hub-first copy) give
+    the oracle's distances bit for bit; then the replayed step graph after the verbose runs."""
+    from ldbc_graphalytics_platforms_graphblas_amd import algorithms as A
+    g = _rmat(10, 8, 8, weighted=True)
+    G = A.Graph(ctx, g.csr, g.directed)
+    try:
+        monkeypatch.setenv("GX_SSSP_VERBOSE", level)
+        capfd.readouterr()
+        for s in (_src(g), 0):
+            got = A.LA_SSSP(G, s)
+            err = capfd.readouterr().err.splitlines()
+            np.testing.assert_array_equal(got, O.sssp(g.csr, s))
+            assert sum(ln.startswith("gx_sssp: delta ") for ln in err) == 1, err
+            steps = [ln for ln in err if ln.startswith("step ")]
+            if level == "2":
+                assert steps and all(all(t in ln for t in (" bucket ", " mode ", " us items ")) for ln in steps), err
+            else:
+                assert not steps, err
+        monkeypatch.delenv("GX_SSSP_VERBOSE")
+        np.testing.assert_array_equal(A.LA_SSSP(G, _src(g)), O.sssp(g.csr, _src(g)))
+        assert not any(ln.startswith(("gx_sssp: delta ", "step ")) for ln in capfd.readouterr().err.splitlines())
+    finally:
+        G.close()
+
+
 @pytest.mark.parametrize("mode", ["0", "1", "2"])
 def test_bfs_directed_transpose_policy(ctx, monkeypatch, mode):
     """Directed BFS: top-down only (0), bottom-up over the cached transpose from the second run

@@ -33,7 +33,8 @@ GRAPHS = [(10, 8, 1, True), (13, 16, 2, True), (12, 8, 3, False), (14, 6, 4, Fal
 
 
 ENVS = [{}, {"GX_SSSP_DSCALE": "0.25"}, {"GX_SSSP_DSCALE": "40"}, {"GX_SSSP_PULL": "2"}, {"GX_SSSP_PULL": "0"},
-        {"GX_SSSP_FUSE": "1"}, {"GX_SSSP_FUSE": "1", "GX_SSSP_DSCALE": "0.05"}]
+        {"GX_SSSP_FUSE": "1"}, {"GX_SSSP_FUSE": "1", "GX_SSSP_DSCALE": "0.05"},
+        {"GX_SSSP_FUSE": "0"}]   # the split clamps 0 to 1 (gx_sssp.h SsspKnobs::fuse)
 
 
 @pytest.mark.parametrize("scale,ef,seed,und", GRAPHS)
@@ -52,6 +53,58 @@ def test_split_run_one_rank(ctx, monkeypatch, scale, ef, seed, und, env):
             assert np.array_equal(sp.run(src), O.sssp(csr, src))
     finally:
         sp.close()
+        G.close()
+
+
+def test_split_run_verbose(ctx, monkeypatch, capfd):
+    """GX_SPLIT_VERBOSE=1: the run reports its rounds per mode and the mode log on stderr."""
+    from ldbc_graphalytics_platforms_graphblas_amd import algorithms as A
+    monkeypatch.setenv("GX_SPLIT_VERBOSE", "1")
+    csr = rmat(10, 8, 1, undirected=True, weighted=True)
+    G = A.Graph(ctx, csr, False)
+    sp = A.SsspSplit(G)
+    try:
+        capfd.readouterr()
+        assert np.array_equal(sp.run(_src(csr)), O.sssp(csr, _src(csr)))
+        assert "[gx_sssp_split] modes:" in capfd.readouterr().err
+    finally:
+        sp.close()
+        G.close()
+
+
+def _split_delta(sp):
+    import ctypes as C
+    from ldbc_graphalytics_platforms_graphblas_amd import _native as N
+    d = C.c_double(0.0)
+    N.check(N.lib().gx_sssp_split_delta(sp.h, C.byref(d)), "gx_sssp_split_delta")
+    return np.float64(d.value).view(np.uint64)
+
+
+@pytest.mark.parametrize("split_first", [False, True])
+@pytest.mark.parametrize("spec,und", [((10, 8, 1), True), ((10, 6, 3), False)])
+def test_split_and_gx_sssp_share_graph_stats(ctx, spec, und, split_first):
+    """gx_sssp and the split on one resident graph, in both orders: whichever runs first fills the
+    graph's cached mean weight and non-isolated count, and both give the oracle's distances.  Two
+    splits made on one graph get the same bucket width bit for bit."""
+    from ldbc_graphalytics_platforms_graphblas_amd import algorithms as A
+    csr = rmat(*spec, undirected=und, weighted=True)
+    src = _src(csr)
+    want = O.sssp(csr, src)
+    G = A.Graph(ctx, csr, not und)
+    sps = []
+    try:
+        if not split_first:
+            assert np.array_equal(A.LA_SSSP(G, src), want)
+        sps += [A.SsspSplit(G), A.SsspSplit(G)]
+        assert _split_delta(sps[0]) == _split_delta(sps[1])
+        assert np.array_equal(sps[0].run(src), want)
+        for _ in range(2):   # on the graph itself, then (undirected) on its hub-first copy
+            assert np.array_equal(A.LA_SSSP(G, src), want)
+        assert np.array_equal(sps[1].run(src), want)
+        assert _split_delta(sps[0]) == _split_delta(sps[1])   # both rebuilt on the same copy
+    finally:
+        for sp in sps:
+            sp.close()
         G.close()
 
 
