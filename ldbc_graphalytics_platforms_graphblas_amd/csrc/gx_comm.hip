@@ -191,6 +191,7 @@ struct PrDist {
     hipGraphExec_t gexec = nullptr;
     hipGraph_t graph = nullptr;
     int g_iters = -1;
+    bool g_first = false;              // the captured run starts with pr_first (ensure_first)
     hipStream_t g_stream = nullptr;
     hipStream_t last_stream = nullptr;
     // one-shot peer-to-peer exchange (gx_pr_dist_create_p2p): flags[p * world + q] = the last
@@ -256,7 +257,29 @@ struct PrDist {
         return GX_SUCCESS;
     }
 
-    int enqueue(int iters, hipStream_t s) {
+    // The first iteration in closed form (PrPart::S) for a runner that exchanges by device copies:
+    // every piece's S, built once by one iteration in S mode over the same buffers and exchange as
+    // a run's first.  Never under capture: run() calls this first.  False: a piece has the closed
+    // form off (GX_PR_FIRST=0, or no memory for its S) and the runs start with pr_init as before.
+    int ensure_first(hipStream_t s, bool *ok) {
+        *ok = false;
+        if (comm || p2p) return GX_SUCCESS;
+        const int np = (int)pieces.size();
+        bool ready = true;
+        for (int p = 0; p < np; p++) {
+            if (!pr_first_alloc(pieces[p])) return GX_SUCCESS;
+            ready = ready && pieces[p]->first_ready;
+        }
+        *ok = true;
+        if (ready) return GX_SUCCESS;
+        if (np == 1) return pr_first_build(pieces[0], xa.p, xb.p, s);
+        for (int p = 0; p < np; p++) GX_TRY(pr_first_init(pieces[p], xl[p]->p, s));
+        for (int p = 0; p < np; p++) GX_TRY(gather(p, xa.p, s, 0));
+        for (int p = 0; p < np; p++) GX_TRY(pr_first_step(pieces[p], xa.p, xl[p]->p, s));
+        return GX_SUCCESS;
+    }
+
+    int enqueue(int iters, hipStream_t s, bool first) {
         const int np = (int)pieces.size();
         const bool swap_only = !comm && !p2p && np == 1;   // one rank, one piece: no exchange at all
         double *xr = xa.p, *xw = xb.p;
@@ -269,12 +292,23 @@ struct PrDist {
                                (uint64_t)0, (uint64_t)1, seq.p + 1, polls);
             GX_TRY(check_launch("k_p2p_wait"));
         }
-        for (int p = 0; p < np; p++) GX_TRY(pr_init(pieces[p], swap_only ? xr : xl[p]->p, s));
-        if (!swap_only) {
-            for (int p = 0; p < np; p++) GX_TRY(gather(p, xr, s, 0));
-            GX_TRY(join(s, 0));
+        if (first) {
+            // pr_init and iteration 1 as one streaming kernel per piece (device copies only: no join)
+            uint64_t nd_total = 0;
+            for (int p = 0; p < np; p++) nd_total += pieces[p]->nd;
+            const bool only = iters == 1;
+            for (int p = 0; p < np; p++)
+                GX_TRY(pr_first(pieces[p], nd_total, swap_only ? xr : xl[p]->p, only ? ro[p]->p : nullptr, s));
+            if (!swap_only && !only)
+                for (int p = 0; p < np; p++) GX_TRY(gather(p, xr, s, 1));
+        } else {
+            for (int p = 0; p < np; p++) GX_TRY(pr_init(pieces[p], swap_only ? xr : xl[p]->p, s));
+            if (!swap_only) {
+                for (int p = 0; p < np; p++) GX_TRY(gather(p, xr, s, 0));
+                GX_TRY(join(s, 0));
+            }
         }
-        for (int it = 0; it < iters; it++) {
+        for (int it = first ? 1 : 0; it < iters; it++) {
             const bool last = it == iters - 1;
             for (int p = 0; p < np; p++) {
                 double *out = swap_only ? xw : xl[p]->p;
@@ -295,16 +329,19 @@ struct PrDist {
 
     int run(int iters, bool use_graph, hipStream_t s) {
         last_stream = s;
+        // before any capture: the captured graph holds k_pr_first and iters - 1 iterations
+        bool first = false;
+        GX_TRY(ensure_first(s, &first));
         // kernel timing brackets launches with events, which a replayed graph would not
         // refresh: timed runs go through direct launches
-        if (!use_graph || ctx->timing) return enqueue(iters, s);
-        if (!gexec || g_iters != iters || g_stream != s) {
+        if (!use_graph || ctx->timing) return enqueue(iters, s, first);
+        if (!gexec || g_iters != iters || g_stream != s || g_first != first) {
             if (gexec) (void)hipGraphExecDestroy(gexec);
             if (graph) (void)hipGraphDestroy(graph);
             gexec = nullptr;
             graph = nullptr;
             GX_HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue(iters, s);
+            const int rc = enqueue(iters, s, first);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (rc != GX_SUCCESS) {
@@ -316,6 +353,7 @@ struct PrDist {
             GX_HIP_TRY(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
             g_iters = iters;
             g_stream = s;
+            g_first = first;
         }
         GX_HIP_TRY(hipGraphLaunch(gexec, s));
         return GX_SUCCESS;

@@ -208,6 +208,13 @@ struct PrPart {
     uint32_t iso_units = 0, iso_dblocks = 0;
     uint64_t iso_rows = 0;
     int kernel = 2;              // 1 = k_pr_pull (CSR-Adaptive, GX_PR_KERNEL=adaptive), 2 = k_pr_pull_units
+    // first iteration in closed form (GX_PR_FIRST, pr_first_build / pr_first): S[i] = the sum of
+    // 1 / outdeg over row i's in-neighbours, S[rows] = the sum of S over the dangling rows.  It
+    // depends on the graph alone, so a resident plan builds it in its first run and every run
+    // starts from r1 = t1 + d/n S in one streaming kernel instead of k_pr_init + an SpMV.
+    bool first_on = true;        // GX_PR_FIRST (read with the kernel choice, pr_plan); off once S cannot be allocated
+    bool first_ready = false;    // S holds the plan's values
+    DBuf<double> S;              // rows + 1 doubles, allocated by the first run (pr_first_alloc)
     // where the sorted plan reads its entries: local row i is row order[i] of (src_rp, src_ci)
     // with every column c renamed perm[c] (gx_pagerank's hub-first plan), or row i itself with
     // its columns as stored (order / perm null: a partition already in its final order)
@@ -265,7 +272,12 @@ int pr_plan(PrPart *p, HostView<int64_t> h_rp, const int64_t *d_rp,
 
 // Column-sorted block plan (gx_pr_plan.hip) and its iteration (k_pr_pull_units, gx_pr_sorted.hip).
 int pr_plan_sorted(PrPart *p, HostView<int64_t> h_rp, HostView<int32_t> h_outdeg);
-int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s);
+// The scalars of one launch when they are not the plan's own (pr_first_build's S mode).
+struct PrScalars {
+    double teleport0, damping_over_n, damping;
+};
+int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s,
+                   const PrScalars *ov = nullptr);
 // Dangling-score sum of this rank into x_local's last chunk slot.
 int pr_dangling(PrPart *p, double *x_local, hipStream_t s);
 
@@ -348,6 +360,19 @@ int pr_part_build(gx_ctx *ctx, uint64_t n_global, int nranks, int rank, uint64_t
 int pr_part_build_rows(gx_ctx *ctx, const gx_csr *A, int nranks, int rank, uint64_t chunk,
                        const std::vector<int32_t> &rows, const int32_t *colmap, double damping, bool force_huge,
                        PrPart **out);
-int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s);
+int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s,
+            const PrScalars *ov = nullptr);
+
+// The first iteration in closed form (PrPart::S).  A runner whose pieces all answer true to
+// pr_first_alloc builds S once, outside any stream capture: pr_first_init for every piece, its
+// exchange of the chunks, then pr_first_step for every piece (x_local: any chunk the runner may
+// overwrite); pr_first_build is both for a plan that is its own exchange.  From then on
+// pr_first starts a run: x of iteration 1 into x_local, its dangling slot included (nd_total: the
+// dangling rows of all pieces), and the scores into rank_out when it is not null.
+bool pr_first_alloc(PrPart *p);
+int pr_first_init(PrPart *p, double *x_local, hipStream_t s);
+int pr_first_step(PrPart *p, const double *x_full, double *x_local, hipStream_t s);
+int pr_first_build(PrPart *p, double *x_in, double *x_out, hipStream_t s);
+int pr_first(PrPart *p, uint64_t nd_total, double *x_local, double *rank_out, hipStream_t s);
 
 }  // namespace gx

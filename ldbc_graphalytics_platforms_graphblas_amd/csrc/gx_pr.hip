@@ -299,6 +299,25 @@ __global__ void k_pr_init(const int32_t *__restrict__ outdeg, int64_t rows, doub
     if (blockIdx.x == 0 && threadIdx.x == 0) x[slot] = dangling0;
 }
 
+// k_pr_init and the first iteration in one pass (PrPart::S): x0(u) = d / (n outdeg(u)) is the
+// graph's up to a scalar, so r1 = t1 + d/n S with t1 = (1-d)/n + d/n nd/n (nd: the dangling rows
+// of all ranks) and S = A (1/outdeg), and x1 = r1 / (outdeg / d) (dangling rows: r1 itself).
+// 20 B per row (out-degree, S, x; 8 more when the scores are asked for, a run of one iteration).
+// The chunk's dangling slot = the sum of r1 over this rank's nd_local dangling rows.  The padding
+// slots (the kernels' zero column among them) are not written.
+__global__ void k_pr_first(const int32_t *__restrict__ outdeg, const double *__restrict__ S, int64_t rows, double t1,
+                           double damping_over_n, double damping, double nd_local, double *x, int64_t slot,
+                           double *rank_out, double *xd, int64_t live) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t deg = outdeg[i];
+        const double r = t1 + damping_over_n * S[i];
+        if (rank_out) rank_out[i] = r;
+        store_x(x, xd, live, i, deg > 0 ? r / ((double)deg / damping) : r);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) x[slot] = nd_local * t1 + damping_over_n * S[rows];
+}
+
 }  // namespace
 
 int pr_plan(PrPart *p, HostView<int64_t> h_rp, const int64_t *d_rp, const int32_t *d_ci,
@@ -313,6 +332,8 @@ int pr_plan(PrPart *p, HostView<int64_t> h_rp, const int64_t *d_rp, const int32_
     // kernel choice: GX_PR_KERNEL = sorted (default) | adaptive (CSR-Adaptive k_pr_pull: row-order
     // sums, bitwise deterministic, ~3x slower)
     if (const char *e = std::getenv("GX_PR_KERNEL")) p->kernel = std::strcmp(e, "adaptive") == 0 ? 1 : 2;
+    // GX_PR_FIRST=0: every run starts with k_pr_init and a full first iteration (no cached S)
+    p->first_on = env_int("GX_PR_FIRST", 1, 0, 1) == 1;
     PlanClock clk("pr_plan", p->ctx->stream);
     if (p->kernel == 1) {
         const int64_t NB = kStreamNnz;
@@ -436,8 +457,58 @@ int pr_init(PrPart *p, double *x_local, hipStream_t s) {
     return check_launch("k_pr_init");
 }
 
-int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s) {
-    if (p->kernel == 2) return pr_step_sorted(p, x_full, x_local, rank_out, s);
+// S, on the first run that wants it.  A failed allocation turns the closed form off for this
+// plan: its runs go on as without S, and the launch checks must not see the allocation's error.
+bool pr_first_alloc(PrPart *p) {
+    if (!p->first_on) return false;
+    if (p->S.p) return true;
+    if (p->S.alloc(p->rows + 1) != GX_SUCCESS) {
+        (void)hipGetLastError();
+        p->first_on = false;
+        return false;
+    }
+    return true;
+}
+
+// S mode's input: x = 1 / outdeg (k_pr_init with n = 1, d = 1), dangling slot 0.  The dangling
+// rows hold 1.0, which nobody gathers.
+int pr_first_init(PrPart *p, double *x_local, hipStream_t s) {
+    p->first_ready = false;
+    hipLaunchKernelGGL(k_pr_init, dim3(grid_for(p->rows, 256, 8192)), dim3(256), 0, s, p->outdeg,
+                       (int64_t)p->rows, 1.0, 1.0, x_local, (int64_t)p->chunk - 1, 0.0, p->xd.p, (int64_t)p->live);
+    return check_launch("k_pr_init");
+}
+
+// S mode's iteration: teleport 0 and damping 1 make the scores the plain sums S, written as the
+// launch's scores (so every item runs, the closed-form isolated blocks too: S = 0), and the
+// launch's dangling sum is S over the dangling rows, since a dangling row's x is its score.
+int pr_first_step(PrPart *p, const double *x_full, double *x_local, hipStream_t s) {
+    const PrScalars ov = {0.0, 0.0, 1.0};
+    GX_TRY(pr_step(p, x_full, x_local, p->S.p, s, &ov));
+    GX_HIP_TRY(hipMemcpyAsync(p->S.p + p->rows, x_local + p->chunk - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
+    p->first_ready = true;
+    return GX_SUCCESS;
+}
+
+int pr_first_build(PrPart *p, double *x_in, double *x_out, hipStream_t s) {
+    GX_TRY(pr_first_init(p, x_in, s));
+    return pr_first_step(p, x_in, x_out, s);
+}
+
+int pr_first(PrPart *p, uint64_t nd_total, double *x_local, double *rank_out, hipStream_t s) {
+    const double dn = (double)p->n_global;
+    const double t1 = (1.0 - p->damping) / dn + p->damping / dn * ((double)nd_total / dn);
+    {
+        KTimer kt(p->ctx, "pr_first", s);
+        hipLaunchKernelGGL(k_pr_first, dim3(grid_for(p->rows, 256, 8192)), dim3(256), 0, s, p->outdeg, p->S.p,
+                           (int64_t)p->rows, t1, p->damping / dn, p->damping, (double)p->nd, x_local,
+                           (int64_t)p->chunk - 1, rank_out, p->xd.p, (int64_t)p->live);
+    }
+    return check_launch("k_pr_first");
+}
+
+int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s, const PrScalars *ov) {
+    if (p->kernel == 2) return pr_step_sorted(p, x_full, x_local, rank_out, s, ov);
     const double dn = (double)p->n_global;
     PullArgs a;
     a.blocks = p->blocks.p;
@@ -453,6 +524,11 @@ int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, 
     a.teleport0 = (1.0 - p->damping) / dn;
     a.damping_over_n = p->damping / dn;
     a.damping = p->damping;
+    if (ov) {   // pr_first_build's S mode
+        a.teleport0 = ov->teleport0;
+        a.damping_over_n = ov->damping_over_n;
+        a.damping = ov->damping;
+    }
     a.long_first = p->long_first.p;
     a.long_nseg = p->long_nseg.p;
     a.long_part = p->long_part.p;
@@ -1091,8 +1167,17 @@ extern "C" int gx_pagerank(gx_graph *g, double damping, int iters, double *rank)
     PrPart *p = g->pr;
     p->damping = damping;
     double *cur = p->xa.p, *nxt = p->xb.p;
-    GX_TRY(pr_init(p, cur, s));
-    for (int it = 0; it < iters; it++) {
+    // iteration 1 in closed form from the plan's S, which the plan's first run builds with the
+    // SpMV launch that iteration would have been (GX_PR_FIRST=0, or no memory for S: as before)
+    int it0 = 0;
+    if (iters >= 1 && pr_first_alloc(p)) {
+        if (!p->first_ready) GX_TRY(pr_first_build(p, cur, nxt, s));
+        GX_TRY(pr_first(p, p->nd, cur, iters == 1 ? p->rank_out.p : nullptr, s));
+        it0 = 1;
+    } else {
+        GX_TRY(pr_init(p, cur, s));
+    }
+    for (int it = it0; it < iters; it++) {
         GX_TRY(pr_step(p, cur, nxt, it == iters - 1 ? p->rank_out.p : nullptr, s));
         std::swap(cur, nxt);
     }

@@ -1026,8 +1026,14 @@ int dump_unit_times(const PrPart *p, uint32_t nw, const char *path_fmt, hipStrea
 
 }  // namespace
 
-int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s) {
+int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s,
+                   const PrScalars *ov) {
     SortedArgs a = sorted_args(p, x_full, x_local, rank_out);
+    if (ov) {   // pr_first_build's S mode: the same launch with other scalars
+        a.teleport0 = ov->teleport0;
+        a.damping_over_n = ov->damping_over_n;
+        a.damping = ov->damping;
+    }
     // a pair slot's one load reads x[2p] and x[2p + 1]
     if ((p->npair || p->nrun) && (reinterpret_cast<uintptr_t>(x_full) & 15))
         return fail(GX_INVALID_VALUE, "pr_step_sorted: pair slots and run groups need x 16-byte aligned");
