@@ -720,6 +720,52 @@ def test_multi_virtual_devices_edge_cases():
             c.close()
 
 
+@pytest.mark.gpu
+def test_multi_virtual_devices_edge_cases_bfs_wcc_cdlp(monkeypatch):
+    """gx_bfs_multi / gx_wcc_multi / gx_cdlp_multi on degenerate shapes: 8 virtual devices over 5
+    vertices (most ranges empty, the largest 1 or 2 vertices, the BFS bitmap a single word), an
+    edgeless graph on 3, every exchange form, BFS from a path vertex and from an isolated one,
+    CDLP with and without iterations; bit for bit against the oracle.  n = 0: WCC and CDLP succeed,
+    BFS refuses its source (always out of range)."""
+    import ctypes as C
+    from ldbc_graphalytics_platforms_graphblas_amd import _native as N
+    from ldbc_graphalytics_platforms_graphblas_amd.algorithms import Context
+    from ldbc_graphalytics_platforms_graphblas_amd.graphio import CSR
+    # a 5-vertex path 0-1-2 plus two isolated vertices, undirected
+    tiny = CSR(5, np.array([0, 1, 3, 4, 4, 4], dtype=np.uint64), np.array([1, 0, 2, 1], dtype=np.uint64))
+    empty = CSR(4, np.zeros(5, dtype=np.uint64), np.zeros(0, dtype=np.uint64))
+    cases = [(tiny, 0, 8, (2, 4)), (empty, 1, 3, (2, 0))]
+    want = [{"bfs": [O.bfs(g, s) for s in srcs], "wcc": O.wcc(g).astype(np.int64),
+             "cdlp": [O.cdlp(g, bool(directed), it).astype(np.int64) for it in (10, 0)]}
+            for g, directed, _, srcs in cases]
+    ctxs = [Context(0) for _ in range(8)]
+    try:
+        for exchange in ("auto", "sparse", "dense"):
+            monkeypatch.setenv("GX_EXCHANGE", exchange)
+            for (g, directed, k, srcs), w in zip(cases, want):
+                sub = ctxs[:k]
+                for src, lv in zip(srcs, w["bfs"]):
+                    got = _multi_out("gx_bfs_multi", sub, g, np.int64, directed, src)
+                    assert np.array_equal(got, lv), (exchange, g.n, src)
+                got = _multi_out("gx_wcc_multi", sub, g, np.uint64, directed)
+                assert np.array_equal(got.astype(np.int64), w["wcc"]), (exchange, g.n)
+                for it, lab in zip((10, 0), w["cdlp"]):
+                    got = _multi_out("gx_cdlp_multi", sub, g, np.uint64, directed, it)
+                    assert np.array_equal(got.astype(np.int64), lab), (exchange, g.n, it)
+        monkeypatch.delenv("GX_EXCHANGE")
+        none = CSR(0, np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint64))
+        s = none.as_c()
+        arr = (C.c_void_p * len(ctxs))(*[c.handle.value for c in ctxs])
+        u64 = np.zeros(1, dtype=np.uint64)
+        i64 = np.zeros(1, dtype=np.int64)
+        assert N.lib().gx_wcc_multi(arr, len(ctxs), C.byref(s), 0, u64.ctypes.data_as(C.POINTER(C.c_uint64))) == 0
+        assert N.lib().gx_cdlp_multi(arr, len(ctxs), C.byref(s), 0, 10, u64.ctypes.data_as(C.POINTER(C.c_uint64))) == 0
+        assert N.lib().gx_bfs_multi(arr, len(ctxs), C.byref(s), 0, 0, i64.ctypes.data_as(C.POINTER(C.c_int64))) != 0
+    finally:
+        for c in ctxs:
+            c.close()
+
+
 def test_multi_rejects_bad_contexts():
     """gx_lcc_multi / gx_pagerank_multi refuse null contexts and ndev < 1 before any device
     work (no GPU needed)."""
