@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void k_rows_sorted(const int32_t *__restrict__
 }
 
 // Hub-first relabelling of a CSR: keys[e] = perm[row] << 32 | perm[col], sorted into the
-// relabelled CSR (the PageRank plan's transform, gx_pr.hip).
+// relabelled CSR (the PageRank plan's transform, gx_pr_order.hip).
 __global__ void k_cdlp_permute_keys(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, int64_t n,
                                     int64_t nnz, const int32_t *__restrict__ perm, uint64_t *__restrict__ keys) {
     constexpr int kPer = 16;
@@ -438,7 +438,7 @@ int cdlp_relabel_csr(const DevCSR &M, int64_t n, const int32_t *perm, DBuf<int64
 }
 
 // Hub-first order by total degree (out + in), ties by id: the most gathered labels share the
-// first lines of the label array (the PageRank plan's order, gx_pr.hip hub_order).
+// first lines of the label array (the PageRank plan's order, gx_pr_order.hip hub_order).
 int cdlp_relabel(gx_graph *g, CdlpCache &C, hipStream_t s) {
     const int64_t n = (int64_t)g->n;
     std::vector<int64_t> deg(n);

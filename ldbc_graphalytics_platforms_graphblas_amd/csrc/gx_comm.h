@@ -55,7 +55,8 @@ struct MultiKnobs {
     bool by_blocks;      // ... its block partition instead of the interleaved one
     bool by_rows;        // ... its partitioned upload
     bool force_dense, force_sparse;   // GX_EXCHANGE = dense / sparse (WordExchange::run); anything else: by size
-    bool plan_times;     // GX_PLAN_TIMES set: the [multi] upload line and WordExchange::report on stderr
+    bool plan_times;     // GX_PLAN_TIMES not 0 (pr.plan_times): the [multi] upload line and WordExchange::report on stderr
+    PrKnobs pr;          // gx_pagerank_multi: the PageRank driver's own knobs (pr_knobs), passed to its plans
 };
 MultiKnobs multi_knobs(int ndev, bool directed, uint64_t nnz, int num_cus);
 

@@ -29,11 +29,12 @@ MultiKnobs multi_knobs(int ndev, bool directed, uint64_t nnz, int num_cus) {
     // (pr_multi_plan).
     k.by_rows = !directed;
     if (const char *e = std::getenv("GX_PR_MULTI_UPLOAD")) k.by_rows = k.by_rows && std::strcmp(e, "whole") != 0;
-    if (const char *e = std::getenv("GX_PR_KERNEL")) k.by_rows = k.by_rows && std::strcmp(e, "adaptive") != 0;   // reads raw columns
+    k.pr = pr_knobs();
+    k.by_rows = k.by_rows && !k.pr.adaptive;   // the adaptive plan is built from a resident graph
     const char *ex = std::getenv("GX_EXCHANGE");
     k.force_dense = ex && std::strcmp(ex, "dense") == 0;
     k.force_sparse = ex && std::strcmp(ex, "sparse") == 0;
-    k.plan_times = std::getenv("GX_PLAN_TIMES") != nullptr;
+    k.plan_times = k.pr.plan_times != 0;
     return k;
 }
 
@@ -107,19 +108,19 @@ struct MultiRun {
     int partition() {
         const uint64_t n = A->n;
         const uint64_t nlive = host_count_live(A->rowptr, n);
-        chunk = ((nlive + V - 1) / V + 2 + 31) / 32 * 32;
+        chunk = pr_chunk((nlive + V - 1) / V);
         if (k.by_rows) {
             if (A->rowptr[0] != 0 || A->rowptr[n] != A->nnz || !host_monotone(A->rowptr, n))
                 return fail(GX_INVALID_VALUE, "gx_pagerank_multi: inconsistent row pointers");
         }
         if (k.by_blocks) {
-            GX_TRY(pr_multi_blocks(A, directed, V, &mb));
+            GX_TRY(pr_multi_blocks(A, directed, V, k.pr, &mb));
             chunk = mb.chunk;
         } else if (k.by_rows) {
             GX_TRY(pr_multi_interleave(A, V, &mb));
             if (mb.chunk != chunk) return fail(GX_PANIC, "gx_pagerank_multi: interleaved chunk mismatch");
         }
-        if (chunk * (uint64_t)V >= (1ull << 31)) return fail(GX_NOT_IMPLEMENTED, "gx_pagerank_multi: exchange too large");
+        if (!pr_chunk_fits(chunk, V)) return fail(GX_NOT_IMPLEMENTED, "gx_pagerank_multi: exchange too large");
         if (k.by_rows) {
             colmap.resize(n);
             host_compose(mb.slot.data(), mb.perm.data(), n, colmap.data());
@@ -156,9 +157,10 @@ struct MultiRun {
                     pc.vrows.resize(pos.size());
                     for (size_t j = 0; j < pos.size(); j++) pc.vrows[j] = mb.order[pos[j]];
                     for (int32_t v : pc.vrows) pc.picked += A->rowptr[v + 1] - A->rowptr[v];
-                    GX_TRY(pr_part_build_rows(ctxs[d], A, V, vr, chunk, pc.vrows, cmap[d].p, damping, k.by_blocks, &pc.part));
+                    GX_TRY(pr_part_build_rows(ctxs[d], A, V, vr, chunk, pc.vrows, cmap[d].p, damping, k.by_blocks, k.pr,
+                                              &pc.part));
                 } else {
-                    GX_TRY(pr_multi_plan(G.g[d], V, vr, chunk, damping, k.by_blocks ? &mb : nullptr, &pc.part));
+                    GX_TRY(pr_multi_plan(G.g[d], V, vr, chunk, damping, k.by_blocks ? &mb : nullptr, k.pr, &pc.part));
                 }
                 pc.rows = pc.part->rows;
                 GX_TRY(pc.xl.alloc(chunk));

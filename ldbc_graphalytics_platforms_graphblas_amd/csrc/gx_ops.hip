@@ -342,7 +342,7 @@ int op_vector(gx_graph *g, int sr, int vxm, int desc, const uint8_t *mask, const
     GX_TRY(hit.alloc((size_t)n));
     const bool pr_path = sr == kPlusSecondF64 && !vxm && use_t;   // t = A' u: the PageRank product
     if (pr_path) {
-        if (!g->pr) GX_TRY(pr_single_plan(g, &g->pr));
+        if (!g->pr) GX_TRY(pr_single_plan(g, pr_knobs(), &g->pr));
         PrPart *p = g->pr;
         const double damping = p->damping;
         p->damping = 1.0;   // teleport (1-d)/n = 0, no dangling mass: r = the gathered sum

@@ -4,6 +4,8 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <memory>
 #include <vector>
 
 #include <algorithm>
@@ -15,16 +17,22 @@ namespace gx {
 // GX_PLAN_TIMES=1: the host-side phase times of a plan build on stderr (the stream is
 // synchronised at every mark, so device phases are attributed too).  Diagnostics only.
 // GX_PLAN_TIMES=2: host time only, no stream synchronisation (the phases' host-side cost,
-// without perturbing a call whose upload overlaps its plan).
+// without perturbing a call whose upload overlaps its plan).  host_only: a build that runs
+// on no stream (pr_multi_blocks), timed by the host clock at either level.
 struct PlanClock {
     bool on = false, sync = true;
     hipStream_t s = nullptr;
     const char *what = "";
     std::chrono::steady_clock::time_point t;
-    PlanClock(const char *w, hipStream_t st) : s(st), what(w) {
+    static int level() {   // 0 off, 1 synchronised marks, 2 host time only
         const char *e = std::getenv("GX_PLAN_TIMES");
-        on = e && std::atoi(e) != 0;
-        sync = !(e && std::atoi(e) == 2);
+        const int v = e ? std::atoi(e) : 0;
+        return v == 0 ? 0 : v == 2 ? 2 : 1;
+    }
+    PlanClock(const char *w, hipStream_t st, bool host_only = false) : s(st), what(w) {
+        const int l = level();
+        on = l != 0;
+        sync = l != 2 && !host_only;
         if (on) {
             if (sync) (void)hipStreamSynchronize(s);
             t = std::chrono::steady_clock::now();
@@ -207,12 +215,13 @@ struct PrPart {
     // them out and adds iso_rows * teleport to the dangling sum instead
     uint32_t iso_units = 0, iso_dblocks = 0;
     uint64_t iso_rows = 0;
-    int kernel = 2;              // 1 = k_pr_pull (CSR-Adaptive, GX_PR_KERNEL=adaptive), 2 = k_pr_pull_units
+    int kernel = 2;              // 1 = k_pr_pull (CSR-Adaptive, GX_PR_KERNEL=adaptive), 2 = k_pr_pull_units;
+                                 // set by the plan that lays the matrix out (pr_new_part), obeyed by pr_plan
     // first iteration in closed form (GX_PR_FIRST, pr_first_build / pr_first): S[i] = the sum of
     // 1 / outdeg over row i's in-neighbours, S[rows] = the sum of S over the dangling rows.  It
     // depends on the graph alone, so a resident plan builds it in its first run and every run
     // starts from r1 = t1 + d/n S in one streaming kernel instead of k_pr_init + an SpMV.
-    bool first_on = true;        // GX_PR_FIRST (read with the kernel choice, pr_plan); off once S cannot be allocated
+    bool first_on = true;        // GX_PR_FIRST (pr_new_part); off once S cannot be allocated
     bool first_ready = false;    // S holds the plan's values
     DBuf<double> S;              // rows + 1 doubles, allocated by the first run (pr_first_alloc)
     // where the sorted plan reads its entries: local row i is row order[i] of (src_rp, src_ci)
@@ -266,7 +275,9 @@ struct HostView {
 };
 
 // Build the row-block plan and dangling list from a local pull CSR (host row pointers
-// h_rp, device rp/ci) and device out-degrees.  Borrowed device pointers must outlive it.
+// h_rp, device rp/ci) and device out-degrees, for the kernel the part records (p->kernel; the
+// adaptive one needs d_ci, the sorted one reads its entries through p->src_*).  Borrowed device
+// pointers must outlive it.
 int pr_plan(PrPart *p, HostView<int64_t> h_rp, const int64_t *d_rp,
             const int32_t *d_ci, const int32_t *d_outdeg, HostView<int32_t> h_outdeg);
 
@@ -282,9 +293,11 @@ int pr_step_sorted(PrPart *p, const double *x_full, double *x_local, double *ran
 int pr_dangling(PrPart *p, double *x_local, hipStream_t s);
 
 int pr_init(PrPart *p, double *x_local, hipStream_t s);
+struct PrKnobs;
 // gx_pagerank's single-rank plan of a graph: its pull matrix (A' when directed, which must be
-// built) relabelled hub-first, column-sorted blocks, x buffers and the hub-first perm.
-int pr_single_plan(gx_graph *g, PrPart **out);
+// built) relabelled hub-first, column-sorted blocks (k.adaptive: the relabelled CSR itself), x
+// buffers and the hub-first perm.
+int pr_single_plan(gx_graph *g, const PrKnobs &k, PrPart **out);
 // Rows of a huge graph's sorted block (kMaxBlockRows below) and its entries.
 constexpr int kPlanBlockRows = 16320;
 constexpr int64_t kPlanBlockNnz = 32 << 20;
@@ -321,10 +334,68 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
 // An integer knob from the environment: dflt when unset or outside [lo, hi].
 inline int env_int(const char *name, int dflt, int lo, int hi) {
     if (const char *e = std::getenv(name)) {
-        const int v = std::atoi(e);
-        if (v >= lo && v <= hi) return v;
+        const long long v = std::atoll(e);
+        if (v >= lo && v <= hi) return (int)v;
     }
     return dflt;
+}
+
+// The PageRank driver's knobs, read once at the top of each entry call (the tests flip them
+// between calls of one process) and passed down; nothing below reads the environment for them.
+struct PrKnobs {
+    bool adaptive;       // GX_PR_KERNEL = sorted (default) | adaptive (CSR-Adaptive k_pr_pull: row-order
+                         // sums, bitwise deterministic, ~3x slower)
+    bool first_on;       // GX_PR_FIRST=0: every run starts with k_pr_init and a full first iteration (no cached S)
+    bool fused;          // GX_PR_FUSED=0: gx_pagerank_csr uploads the whole graph before it plans
+    int plan_times;      // GX_PLAN_TIMES (PlanClock::level)
+    int block_rows;      // GX_PR_MULTI_BLOCK_ROWS / _NNZ: pr_multi_blocks' caps, shrunk by tests
+    int block_nnz;
+};
+inline PrKnobs pr_knobs() {
+    PrKnobs k;
+    const char *e = std::getenv("GX_PR_KERNEL");
+    k.adaptive = e && std::strcmp(e, "adaptive") == 0;
+    k.first_on = env_int("GX_PR_FIRST", 1, 0, 1) == 1;
+    k.fused = env_int("GX_PR_FUSED", 1, 0, 1) == 1;
+    k.plan_times = PlanClock::level();
+    k.block_rows = env_int("GX_PR_MULTI_BLOCK_ROWS", kPlanBlockRows, 1, kPlanBlockRows);
+    k.block_nnz = env_int("GX_PR_MULTI_BLOCK_NNZ", (int)kPlanBlockNnz, 1, 1 << 30);
+    return k;
+}
+
+// A part with its identity: whose rows (rank of nranks over n_global vertices), its exchange
+// chunk and live prefix (~0: every row), and the kernel its creator lays the matrix out for.
+inline std::unique_ptr<PrPart> pr_new_part(gx_ctx *ctx, uint64_t n_global, int nranks, int rank, uint64_t chunk,
+                                           uint64_t live, double damping, bool force_huge, const PrKnobs &k) {
+    std::unique_ptr<PrPart> p(new PrPart());
+    p->ctx = ctx;
+    p->n_global = n_global;
+    p->nranks = nranks;
+    p->rank = rank;
+    p->chunk = chunk;
+    p->live = live;
+    p->damping = damping;
+    p->force_huge = force_huge;
+    p->kernel = k.adaptive ? 1 : 2;
+    p->first_on = k.first_on;
+    return p;
+}
+
+// Doubles of a rank's chunk: its live rows, a zero padding slot (chunk - 2) and the dangling
+// slot (chunk - 1), rounded up to 32.  The exchanged vector's slots are int32 column ids.
+inline uint64_t pr_chunk(uint64_t live_rows) { return (live_rows + 2 + 31) / 32 * 32; }
+inline bool pr_chunk_fits(uint64_t chunk, int nranks) { return chunk * (uint64_t)nranks < (1ull << 31); }
+
+// First position of a non-increasing out-degree sequence that holds 0 (hub-first rows: the
+// dangling rows are a suffix, the rows before it the live prefix); its size when there is none.
+inline uint64_t first_zero(HostView<int32_t> outdeg) {
+    uint64_t lo = 0, hi = outdeg.size();
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (outdeg[mid] == 0) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
 }
 
 // gx_pagerank_multi's block partition (pr_partition.block_relabel restated): the hub-first
@@ -337,7 +408,7 @@ struct MultiBlocks {
     uint64_t chunk = 0;
     std::vector<int32_t> order, perm;   // the host hub-first order: position -> vertex, vertex -> position
 };
-int pr_multi_blocks(const gx_csr *A, int directed, int ndev, MultiBlocks *out);
+int pr_multi_blocks(const gx_csr *A, int directed, int ndev, const PrKnobs &k, MultiBlocks *out);
 // The interleaved partition in the same form: hub-first position h to rank h % ndev as its
 // local row h / ndev (pr_partition.interleaved_relabel).
 int pr_multi_interleave(const gx_csr *A, int ndev, MultiBlocks *out);
@@ -346,20 +417,20 @@ int pr_multi_interleave(const gx_csr *A, int ndev, MultiBlocks *out);
 // directed): hub-first positions d, d + ndev, ... as rows (or mb's blocks), columns in the
 // exchange layout.
 int pr_multi_plan(gx_graph *g, int ndev, int d, uint64_t chunk, double damping, const MultiBlocks *mb,
-                  PrPart **out);
+                  const PrKnobs &k, PrPart **out);
 // A rank's plan from its local pull rows (h_rp from 0) with columns already in the exchange
 // layout (ci), the out-degree of each row's vertex, and its live prefix (gx_pr_part_create_live).
 // force_huge: plan with the whole graph's block cut (a rank of a block partition).
 int pr_part_build(gx_ctx *ctx, uint64_t n_global, int nranks, int rank, uint64_t chunk, uint64_t live,
                   const std::vector<int64_t> &h_rp, const std::vector<int32_t> &ci, const std::vector<int32_t> &h_outdeg,
-                  double damping, PrPart **out, bool force_huge = false);
+                  double damping, const PrKnobs &k, PrPart **out, bool force_huge = false);
 // gx_pagerank_multi's partitioned upload: a rank's rows `rows` (vertex ids of A, an undirected
 // graph's pull rows) picked from the host CSR A straight into the staging buffers (original
 // column ids, narrowed and checked), renamed to the exchange layout by the plan's key pass
 // through colmap (device, n entries: vertex -> owner * chunk + local row).
 int pr_part_build_rows(gx_ctx *ctx, const gx_csr *A, int nranks, int rank, uint64_t chunk,
                        const std::vector<int32_t> &rows, const int32_t *colmap, double damping, bool force_huge,
-                       PrPart **out);
+                       const PrKnobs &k, PrPart **out);
 int pr_step(PrPart *p, const double *x_full, double *x_local, double *rank_out, hipStream_t s,
             const PrScalars *ov = nullptr);
 
