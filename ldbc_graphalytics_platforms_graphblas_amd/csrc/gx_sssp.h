@@ -28,6 +28,14 @@ __device__ __forceinline__ int64_t bucket_of(double d, double inv_delta) {
     return q < 4.0e18 ? (int64_t)q : (int64_t)kMaxBucket;
 }
 
+// A bucket number as a per-vertex stamp: its low 31 bits, so never negative.  A vertex is stamped
+// only for buckets of the current ring window, and a later stamp names a lower bucket that is
+// still ahead of `cur`, so two stamps of one vertex lie fewer than 2 kRing buckets apart and 31
+// bits tell them apart.  The "never stamped" state is a word no bucket produces: negative on the
+// single path (bstamp -1, the bucket half of nsw all ones), 0 on the split, whose tags are
+// ~stamp_of(b), always negative.
+__device__ __forceinline__ int32_t stamp_of(int64_t b) { return (int32_t)((uint32_t)b & 0x7FFFFFFFu); }
+
 // Relax items of a row part of `len` edges: gx_sssp queues none for an empty part, the split one.
 __device__ __forceinline__ uint32_t chunks_of(int64_t len) { return (uint32_t)((len + kChunk - 1) / kChunk); }
 __device__ __forceinline__ uint32_t chunks_min1(int64_t len) {

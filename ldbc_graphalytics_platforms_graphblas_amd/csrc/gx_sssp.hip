@@ -79,9 +79,9 @@ struct SsspBufs {
     const double *w;
     unsigned long long *dist;
     unsigned long long *relaxed;  // distance all edges of v were last relaxed with
-    unsigned long long *nsw;      // (bucket a vertex was last put on the settled list for << 32) |
+    unsigned long long *nsw;      // (stamp_of the bucket a vertex was last put on the settled list for << 32) |
                                   // round it was last queued as near: one word, one exchange
-    int32_t *bstamp;              // bucket a vertex was last put into a ring slot for
+    int32_t *bstamp;              // stamp_of the bucket a vertex was last put into a ring slot for, -1 never
     int32_t *ostamp;              // overflow epoch a vertex was last put on the overflow
     uint32_t *sbits;              // pulled heavy phase: one bit per vertex on the settled list
     uint32_t nbits;               // words of sbits
@@ -97,7 +97,7 @@ struct SsspBufs {
 };
 
 __device__ __forceinline__ unsigned long long nsw_pack(int64_t bucket, int32_t round) {
-    return ((unsigned long long)(uint32_t)bucket << 32) | (uint32_t)round;
+    return ((unsigned long long)(uint32_t)stamp_of(bucket) << 32) | (uint32_t)round;
 }
 
 constexpr int kStatLanes = 256;
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_advance(SsspBufs B) {
     unsigned long long mymin = ~0ull, n_skip = 0;
     const uint32_t stride = gridDim.x * kSsspBlock;
     const uint32_t nround = (dom + stride - 1) / stride;
-    const int32_t lo32 = (int32_t)(cur - (fn - 1));   // the first opened bucket (stamps are 32-bit)
+    const int32_t lo31 = stamp_of(cur - (fn - 1));   // the first opened bucket's stamp
     // pushes are staged per wave in LDS and flushed in bulk, as in k_sssp_relax
     __shared__ Stage stages[kSsspBlock / kWave];
     Stage &sg = stages[threadIdx.x / kWave];
@@ -415,8 +415,10 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_advance(SsspBufs B) {
         if (dense) {
             if (f < dom) {
                 v = (int32_t)f;
-                const uint32_t k = (uint32_t)B.bstamp[v] - (uint32_t)lo32;
-                if (k < (uint32_t)fn) {
+                // stamps count modulo 2^31; a never-stamped vertex (negative) is in no bucket
+                const int32_t sv = B.bstamp[v];
+                const uint32_t k = ((uint32_t)sv - (uint32_t)lo31) & 0x7FFFFFFFu;
+                if (sv >= 0 && k < (uint32_t)fn) {
                     if (B.dist[v] == B.relaxed[v]) {
                         n_skip++;
                     } else {
@@ -455,7 +457,7 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_advance(SsspBufs B) {
                 // slot of the bucket its bstamp names (later pushes only lower it): the others are
                 // skipped without the exchange a claim would cost (3.4 M of them when SYN-8_5's
                 // window opens whole)
-                if (fn == 1 || B.bstamp[v] == (int32_t)(cur - (fn - 1) + fj)) {
+                if (fn == 1 || B.bstamp[v] == stamp_of(cur - (fn - 1) + fj)) {
                     B.nsw[v] = nsw_pack(cur, r);
                     to_near = to_set = true;
                     nch = chunks_of(B.lend[v] - B.rp[v]);
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_advance(SsspBufs B) {
             } else {
                 const int64_t b = max(bucket_of(bitsd(db), B.inv_delta), win_base);
                 if (b < lim) {
-                    B.bstamp[v] = (int32_t)b;
+                    B.bstamp[v] = stamp_of(b);
                     slot = (int)(b % kRing);
                     to_ring = true;
                 } else {
@@ -596,8 +598,8 @@ __device__ __forceinline__ void sssp_pull(const SsspBufs &B, Stage *stages, unsi
             // v0 is this lane's alone in a pull (its candidates met in LDS), so no other lane
             // pushes it in this launch: a plain test and store instead of a claim's exchange
             if (b < lim) {
-                if (B.bstamp[v0] != (int32_t)b) {
-                    B.bstamp[v0] = (int32_t)b;
+                if (B.bstamp[v0] != stamp_of(b)) {
+                    B.bstamp[v0] = stamp_of(b);
                     to_ring = true;
                     slot = (int)(b % kRing);
                 }
@@ -762,7 +764,7 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_relax(SsspBufs B) {
                         } else if (b < lim) {
                             cls[q] = 2;
                             stp[q] = B.bstamp + v[q];
-                            tag[q] = (int32_t)b;
+                            tag[q] = stamp_of(b);
                             slot[q] = (int)(b % kRing);
                         } else {
                             cls[q] = 3;
@@ -800,7 +802,7 @@ __global__ __launch_bounds__(kSsspBlock) void k_sssp_relax(SsspBufs B) {
             for (int q = 0; q < kSlots; q++) {
                 won[q] = cls[q] == 1 ? (uint32_t)nseen[q] != (uint32_t)rn : cls[q] != 0 && seen[q] != tag[q];
                 // near pushes also join the settled list, once per bucket
-                to_set[q] = cls[q] == 1 && won[q] && (uint32_t)(nseen[q] >> 32) != (uint32_t)cur;
+                to_set[q] = cls[q] == 1 && won[q] && (uint32_t)(nseen[q] >> 32) != (uint32_t)stamp_of(cur);
                 rlo[q] = rhi[q] = 0;
                 if (won[q] && cls[q] == 1) {
                     rlo[q] = B.rp[v[q]];
@@ -848,8 +850,8 @@ __global__ void k_sssp_init(unsigned long long *dist, unsigned long long *relaxe
          v += (int64_t)gridDim.x * blockDim.x) {
         dist[v] = 0x7FF0000000000000ull;   // +infinity
         relaxed[v] = ~0ull;                // never equal to a distance
-        nsw[v] = ~0ull;                    // round -1, bucket -1
-        bstamp[v] = -1;
+        nsw[v] = ~0ull;                    // round -1, never on a settled list (no stamp_of value)
+        bstamp[v] = -1;                    // never in a ring slot
         ostamp[v] = 0;
     }
 }

@@ -94,7 +94,7 @@ struct alignas(16) VRec {
 struct alignas(16) SRec {
     int32_t sstamp;   // epoch v joined the settled set
     int32_t hmark;    // round of the HEAVY / PULL phase that relaxed v's heavy edges (0: pending)
-    int32_t bstamp;   // bucket v was last put into a ring slot for (low 32 bits + 1)
+    int32_t bstamp;   // ~stamp_of the bucket v was last put into a ring slot for; 0 never
     int32_t ostamp;   // overflow tag v was last put on the overflow with
 };
 
@@ -187,7 +187,7 @@ __device__ __forceinline__ void tile_stage(const SplitBufs &B, Tile &T, Push &P,
     }
     if (far) {
         if (b < st->win_base + kRing) {
-            const int32_t btag = (int32_t)(uint32_t)b + 1;
+            const int32_t btag = ~stamp_of(b);   // negative: 0 is "never"
             if (r.bstamp != btag) {
                 B.srec[v].bstamp = btag;
                 P.q = (int8_t)(kQRing + (int)(b % kRing));
