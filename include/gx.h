@@ -198,6 +198,39 @@ int gx_ktruss(gx_graph *g, uint32_t k, int64_t *support, uint64_t *stats);
  * cache and knobs as gx_ktruss. */
 int gx_truss_all(gx_graph *g, int64_t *truss, uint64_t *kmax);
 
+/* The role of LAGraph_KCore(&decomp, G, k).  The graph must be undirected with both directions stored
+ * (the caller's contract, as for gx_lcc; it is not verified here, unlike gx_ktruss, which needs the
+ * reverse positions anyway).  An edge is an unordered pair {i, j}, i != j; diagonal entries belong to
+ * no edge and count toward no degree: deg(v) is the number of off-diagonal entries of row v.  The
+ * k-core is the largest subgraph in which every vertex has at least k neighbours inside it (it is
+ * unique).
+ * degree is n int64 or NULL: v's number of neighbours inside the k-core, -1 when v is not in it.
+ * stats is uint64[3] or NULL: stats[0] = the vertices of the k-core, stats[1] = its edges (pairs, not
+ * entries), stats[2] = the rounds of synchronous pruning that removed at least one vertex, round r
+ * removing every vertex whose degree in the graph left by round r - 1 is below k (the count does not
+ * depend on how the implementation schedules its work).  With degree == NULL only the three
+ * statistics cross the host link.  k == 0 keeps every vertex: degree is then the plain off-diagonal
+ * degree and there are 0 rounds.  n == 0 and nnz == 0 succeed.
+ * NULL g, or degree and stats both NULL: GX_NULL_POINTER; a directed graph: GX_INVALID_VALUE; both
+ * before any device work, the outputs untouched.
+ * Runs on g itself (never the hub-first copy) and counts as no BFS, WCC, SSSP or CDLP call on g; the
+ * degrees, the frontier lists and the state are built by the first call and kept with g until
+ * gx_graph_free.  Integers only: the same bit for bit on every run.
+ * The vertices below k are peeled frontier by frontier on the device: a frontier row of at most
+ * GX_CORE_SHORT entries is one thread's, of at most GX_CORE_LONG one wave's, a longer one a
+ * workgroup's.  Rounds are queued GX_CORE_BATCH at a time and the state is read one batch late; while
+ * a frontier holds at most GX_CORE_SOLO vertices (0 = never) one workgroup runs the rounds by itself
+ * (the results, stats[2] included, are identical).  GX_CORE_VERBOSE prints one line per host read to
+ * stderr. */
+int gx_kcore(gx_graph *g, uint32_t k, int64_t *degree, uint64_t *stats);
+/* The role of LAGraph_KCore_All: every k at once, as one number per vertex.  core is n int64 or NULL:
+ * the largest k whose k-core holds v (0 for a vertex with no edge), so core[v] >= k exactly when
+ * gx_kcore(g, k, ..) gives degree[v] >= 0.  kmax (may be NULL, not both) is the largest entry of
+ * core, 0 when there is no edge.  k = 1, 2, ...: pruning to a fixed point at each k with the degrees
+ * carried over; what leaves while pruning toward k gets k - 1, and a level nobody leaves at is jumped
+ * over (k = the smallest alive degree + 1).  Graph, errors, cache and knobs as gx_kcore. */
+int gx_core_all(gx_graph *g, int64_t *core, uint64_t *kmax);
+
 /* LAGr_PageRankGX(&r, &iters, G, damping, itermax) incl. LAGraph_Cached_OutDegree /
  * LAGraph_Cached_AT (pr.cpp:58-61).  Graphalytics PR with dangling redistribution,
  * exactly `iters` iterations, fp64. */

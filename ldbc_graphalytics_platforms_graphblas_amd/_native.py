@@ -73,6 +73,8 @@ SIGNATURES = [
     ("gx_mxm_masked", C.c_int, [_P, C.c_int, C.c_int, _I64P]),
     ("gx_ktruss", C.c_int, [_P, C.c_uint32, _I64P, _U64P]),
     ("gx_truss_all", C.c_int, [_P, _I64P, _U64P]),
+    ("gx_kcore", C.c_int, [_P, C.c_uint32, _I64P, _U64P]),
+    ("gx_core_all", C.c_int, [_P, _I64P, _U64P]),
     ("gx_set_kernel_timing", C.c_int, [_P, C.c_int]),
     ("gx_kernel_stats", C.c_int, [_P, C.c_char_p, _U64P, _DP]),
     ("gx_reset_kernel_stats", C.c_int, [_P]),

@@ -183,6 +183,39 @@ def LA_AllKTruss(G: Graph):
     return truss[:G.nnz], int(kmax.value)
 
 
+# gx_kcore / gx_core_all's row tiers (gx_core.hip kCoreShort / kCoreLong): a frontier vertex whose row has at
+# most CORE_SHORT entries is expanded by one thread, at most CORE_LONG by one wave, a longer one by a
+# workgroup; GX_CORE_SHORT / GX_CORE_LONG override.  GX_CORE_SOLO: the frontier size up to which one
+# workgroup runs the rounds by itself (0 never); GX_CORE_BATCH: the steps queued between two host reads.
+CORE_SHORT, CORE_LONG = 8, 512
+CORE_SOLO, CORE_BATCH = 256, 8
+
+
+def LA_KCore(G: Graph, k: int, degree: bool = True, stats: bool = False):
+    """The role of LAGraph_KCore (gx_kcore) on an undirected graph: degree[n] int64, the vertex's
+    neighbours inside the k-core, -1 where the vertex is not in it; stats[3] uint64 = (vertices, edges,
+    pruning rounds); or both as a tuple.  With degree=False only the statistics leave the device;
+    asking for neither is gx_kcore's GX_NULL_POINTER."""
+    if not 0 <= int(k) < 2 ** 32:
+        raise ValueError("k does not fit uint32")
+    deg = np.empty(max(G.n, 1), dtype=np.int64) if degree else None
+    st = np.zeros(3, dtype=np.uint64) if stats else None
+    N.check(N.lib().gx_kcore(G.handle, int(k), N.as_i64p(deg) if degree else None,
+                             N.as_u64p(st) if stats else None), "gx_kcore")
+    if degree and stats:
+        return deg[:G.n], st
+    return deg[:G.n] if degree else st
+
+
+def LA_CoreAll(G: Graph):
+    """The role of LAGraph_KCore_All (gx_core_all): (core, kmax); core[n] int64 = the largest k whose
+    k-core holds the vertex (0 without an edge), kmax its maximum."""
+    core = np.empty(max(G.n, 1), dtype=np.int64)
+    kmax = C.c_uint64(0)
+    N.check(N.lib().gx_core_all(G.handle, N.as_i64p(core), C.byref(kmax)), "gx_core_all")
+    return core[:G.n], int(kmax.value)
+
+
 def LA_PR(G: Graph, damping_factor: float, iteration_num: int) -> np.ndarray:
     """pr.cpp:47-66: Graphalytics PageRank, fp64."""
     out = np.empty(G.n, dtype=np.float64)

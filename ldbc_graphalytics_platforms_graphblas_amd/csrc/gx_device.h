@@ -222,6 +222,7 @@ struct gx_graph {
     std::shared_ptr<void> cdlp;       // gx_cdlp's tier lists and buffers (gx_cdlp.hip CdlpCache)
     std::shared_ptr<void> lcc;        // gx_lcc's orientation and work items (gx_lcc.hip LccCache)
     std::shared_ptr<void> truss;      // gx_ktruss / gx_truss_all's view, tiers and state (gx_truss.hip TrussCache)
+    std::shared_ptr<void> core;       // gx_kcore / gx_core_all's degrees, frontiers and state (gx_core.hip CoreCache)
     // Hub-first relabelled copy of an undirected graph (gx_runtime.hip hub_for): BFS, WCC and
     // SSSP run on it from their second call on the graph.  perm[v] = v's id in the copy, order
     // its inverse; on the copy, out_perm / out_order point at the parent's perm / order.
@@ -437,6 +438,7 @@ hipError_t warm_bfs(hipStream_t s);
 hipError_t warm_cdlp(hipStream_t s);
 hipError_t warm_cdlp_keep(hipStream_t s);
 hipError_t warm_cdlp_tiers(hipStream_t s);
+hipError_t warm_core(hipStream_t s);
 hipError_t warm_lcc(hipStream_t s);
 hipError_t warm_msbfs(hipStream_t s);
 hipError_t warm_ops(hipStream_t s);
