@@ -254,6 +254,33 @@ int gx_sssp(gx_graph *g, uint64_t src, double *dist);
 /* A LOR A' (directed) + LAGr_ConnectedComponents (wcc.cpp:39-66).  comp[v] = the
  * smallest internal vertex index of v's weakly connected component. */
 int gx_wcc(gx_graph *g, uint64_t *comp);
+/* The role of LAGraph_scc(&result, A): the strongly connected components of a directed graph.  u and v
+ * share a component exactly when each reaches the other over stored entries; diagonal entries change
+ * nothing (a vertex whose only entries are diagonal is a component by itself) and weights are ignored.
+ * comp is n uint64 or NULL: comp[v] = the smallest internal vertex index of v's component, gx_wcc's
+ * labelling rule, so comp_scc[v] >= comp_wcc[v] and every component lies inside one weakly connected
+ * one.  stats is uint64[3] or NULL: stats[0] = the components, stats[1] = the vertices of the largest
+ * one, stats[2] = the single-vertex components, computed on the device; with comp == NULL only these
+ * three words cross the host link.  An undirected graph is accepted (A is its own transpose) and gives
+ * gx_wcc's labels bit for bit.  n == 0 and nnz == 0 succeed; with nnz == 0 every vertex is its own
+ * component.
+ * NULL g, or comp and stats both NULL: GX_NULL_POINTER before any device work, the outputs untouched.
+ * Runs on g itself (never the hub-first copy) and counts as no BFS, WCC, SSSP or CDLP call on g; it
+ * builds and caches the transpose of a directed graph, and its labels, degree words, lists and state
+ * are built by the first call and kept with g until gx_graph_free.  Integers only: the same bit for
+ * bit on every run and under every knob.
+ * Three phases on the device.  Trim: an alive vertex with no alive in- or no alive out-neighbour is a
+ * component by itself, peeled frontier by frontier (GX_SCC_TRIM=0: never run; the colours resolve
+ * them).  Pivot, once: the forward and the backward reach of the alive vertex with the largest
+ * in-degree x out-degree meet in one component (GX_SCC_PIVOT=0: skipped).  Colour: the smallest id
+ * flows forward to a fixed point, every vertex that kept its own id is a root and collects its
+ * component backward inside its colour; then trim again, until nothing is alive.  A walked row of at
+ * most GX_SCC_SHORT entries is one thread's, of at most GX_SCC_LONG one wave's, a longer one a
+ * workgroup's.  Steps are queued GX_SCC_BATCH at a time and the state is read one batch late; a stage
+ * whose work is at most GX_SCC_SOLO items (0 = never) is run by one workgroup, round after round;
+ * GX_SCC_GRID caps the grid of the others.  GX_SCC_VERBOSE prints one line per host read to stderr,
+ * and at the end the microseconds every stage took. */
+int gx_scc(gx_graph *g, uint64_t *comp, uint64_t *stats);
 
 /* LAGraph_cdlp / CUDA_CDLP::LAGraph_cdlp_gpu (cdlp.cpp:54-81; cdlp_cuda.cu:118-251).
  * labels[v] = internal index of v's community label after at most `iters` synchronous

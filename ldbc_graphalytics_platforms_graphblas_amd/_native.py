@@ -66,6 +66,7 @@ SIGNATURES = [
     ("gx_pagerank", C.c_int, [_P, C.c_double, C.c_int, _DP]),
     ("gx_sssp", C.c_int, [_P, C.c_uint64, _DP]),
     ("gx_wcc", C.c_int, [_P, _U64P]),
+    ("gx_scc", C.c_int, [_P, _U64P, _U64P]),
     ("gx_cdlp", C.c_int, [_P, C.c_int, _U64P]),
     ("gx_lcc", C.c_int, [_P, _DP]),
     ("gx_mxv", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

@@ -272,6 +272,30 @@ def WeaklyConnectedComponents(G: Graph) -> np.ndarray:
     return out
 
 
+# gx_scc's row tiers (gx_scc.hip kSccShort / kSccLong): a walked row of at most SCC_SHORT entries is one
+# thread's, of at most SCC_LONG one wave's, a longer one a workgroup's; GX_SCC_SHORT / GX_SCC_LONG override.
+# GX_SCC_SOLO: the work (frontier, alive list or n) up to which one workgroup runs the rounds by itself
+# (0 never); GX_SCC_BATCH: the steps queued between two host reads; GX_SCC_GRID: the cap of the step grid.
+# GX_SCC_TRIM=0 / GX_SCC_PIVOT=0 leave the trim / the pivot phase out; the results are the same under
+# every setting.
+SCC_SHORT, SCC_LONG = 8, 512
+SCC_SOLO, SCC_BATCH = 256, 8
+
+
+def LA_SCC(G: Graph, comp: bool = True, stats: bool = False):
+    """The role of LAGraph_scc (gx_scc): comp[n] uint64, the smallest internal vertex id of the
+    vertex's strongly connected component (gx_wcc's labelling rule); stats[3] uint64 = (components,
+    vertices of the largest, single-vertex components); or both as a tuple.  With comp=False only the
+    statistics leave the device; asking for neither is gx_scc's GX_NULL_POINTER."""
+    out = np.empty(max(G.n, 1), dtype=np.uint64) if comp else None
+    st = np.zeros(3, dtype=np.uint64) if stats else None
+    N.check(N.lib().gx_scc(G.handle, N.as_u64p(out) if comp else None, N.as_u64p(st) if stats else None),
+            "gx_scc")
+    if comp and stats:
+        return out[:G.n], st
+    return out[:G.n] if comp else st
+
+
 def LA_CDLP(G: Graph, itermax: int) -> np.ndarray:
     """cdlp.cpp:54-81: community labels (internal vertex ids)."""
     out = np.empty(G.n, dtype=np.uint64)

@@ -223,6 +223,7 @@ struct gx_graph {
     std::shared_ptr<void> lcc;        // gx_lcc's orientation and work items (gx_lcc.hip LccCache)
     std::shared_ptr<void> truss;      // gx_ktruss / gx_truss_all's view, tiers and state (gx_truss.hip TrussCache)
     std::shared_ptr<void> core;       // gx_kcore / gx_core_all's degrees, frontiers and state (gx_core.hip CoreCache)
+    std::shared_ptr<void> scc;        // gx_scc's labels, degree words, lists and state (gx_scc.hip SccCache)
     // Hub-first relabelled copy of an undirected graph (gx_runtime.hip hub_for): BFS, WCC and
     // SSSP run on it from their second call on the graph.  perm[v] = v's id in the copy, order
     // its inverse; on the copy, out_perm / out_order point at the parent's perm / order.
@@ -449,6 +450,7 @@ hipError_t warm_pr_order(hipStream_t s);
 hipError_t warm_pr_plan(hipStream_t s);
 hipError_t warm_pr_sorted(hipStream_t s);
 hipError_t warm_runtime(hipStream_t s);
+hipError_t warm_scc(hipStream_t s);
 hipError_t warm_sssp(hipStream_t s);
 hipError_t warm_truss(hipStream_t s);
 hipError_t warm_wcc(hipStream_t s);
