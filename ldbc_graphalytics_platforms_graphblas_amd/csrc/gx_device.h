@@ -220,7 +220,7 @@ struct gx_graph {
     int cdlp_calls = 0;         // CDLP runs (the relabelled copy is built from the second)
     gx::SsspLayout *sssp = nullptr;   // cached light/heavy edge layout
     std::shared_ptr<void> cdlp;       // gx_cdlp's tier lists and buffers (gx_cdlp.hip CdlpCache)
-    std::shared_ptr<void> lcc;        // gx_lcc's orientation and work items (gx_lcc.hip LccCache)
+    std::shared_ptr<void> lcc;        // gx_lcc's orientation, dense core and work items (gx_lcc.h LccCache)
     std::shared_ptr<void> truss;      // gx_ktruss / gx_truss_all's view, tiers and state (gx_truss.hip TrussCache)
     std::shared_ptr<void> core;       // gx_kcore / gx_core_all's degrees, frontiers and state (gx_core.hip CoreCache)
     std::shared_ptr<void> scc;        // gx_scc's labels, degree words, lists and state (gx_scc.hip SccCache)
@@ -441,6 +441,9 @@ hipError_t warm_cdlp_keep(hipStream_t s);
 hipError_t warm_cdlp_tiers(hipStream_t s);
 hipError_t warm_core(hipStream_t s);
 hipError_t warm_lcc(hipStream_t s);
+hipError_t warm_lcc_dense(hipStream_t s);
+hipError_t warm_lcc_orient(hipStream_t s);
+hipError_t warm_lcc_part(hipStream_t s);
 hipError_t warm_msbfs(hipStream_t s);
 hipError_t warm_ops(hipStream_t s);
 hipError_t warm_part(hipStream_t s);

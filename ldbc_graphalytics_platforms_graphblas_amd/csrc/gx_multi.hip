@@ -1,8 +1,10 @@
 // gx_multi.hip -- the one-process multi-device drivers (bin/exe/* with GX_NGPUS): gx_pagerank_multi,
 // gx_sssp_multi, gx_lcc_multi, gx_bfs_multi, gx_wcc_multi, gx_cdlp_multi.  Each is the single-device
 // algorithm's partitioned steps on every device, exchanged by the clique of gx_comm.h, which also
-// has the per-device owners and loops they share.
+// has the per-device owners and loops they share.  The partitioned steps themselves are in
+// gx_pr_part.hip, gx_sssp_split.hip, gx_lcc_part.hip (with gx_lcc.h's size check) and gx_part.hip.
 #include "gx_comm.h"
+#include "gx_lcc.h"
 
 namespace gx {
 
@@ -474,7 +476,7 @@ extern "C" int gx_lcc_multi(gx_ctx *const *ctxs, int ndev, const gx_csr *A, int 
     if (!lcc) return fail(GX_NULL_POINTER, "gx_lcc_multi: null argument");
     const uint64_t n = A->n;
     if (n == 0) return GX_SUCCESS;
-    if (n >= (1ull << 29)) return fail(GX_NOT_IMPLEMENTED, "gx_lcc_multi: more than 2^29 vertices (packed oriented entries)");
+    GX_TRY(lcc_check_size(n, "gx_lcc_multi"));
     MultiGraphs G(ndev);
     PerDev<uint64_t> tc(ctxs, ndev);
     PerDevHandle<gx_lcc_part, gx_lcc_part_free> part(ctxs, ndev);

@@ -67,8 +67,8 @@ extern "C" int gx_init(int device, gx_ctx **out) {
         if (e == hipSuccess) e = hipMemcpyAsync(d, ctx->staging[0], 1 << 20, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[1], d, 1 << 20, hipMemcpyDeviceToHost, ctx->stream);
         // load every kernel module now (see GX_MODULE_WARMER)
-        for (auto warm : {warm_bfs, warm_cdlp, warm_cdlp_keep, warm_cdlp_tiers, warm_core, warm_lcc, warm_msbfs, warm_ops,
-                          warm_part, warm_pr, warm_pr_order, warm_pr_plan, warm_pr_sorted, warm_runtime, warm_scc, warm_sssp, warm_sssp_split, warm_truss, warm_wcc})
+        for (auto warm : {warm_bfs, warm_cdlp, warm_cdlp_keep, warm_cdlp_tiers, warm_core, warm_lcc, warm_lcc_dense, warm_lcc_orient,
+                          warm_lcc_part, warm_msbfs, warm_ops, warm_part, warm_pr, warm_pr_order, warm_pr_plan, warm_pr_sorted, warm_runtime, warm_scc, warm_sssp, warm_sssp_split, warm_truss, warm_wcc})
             if (e == hipSuccess) e = warm(ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (d) (void)hipFree(d);

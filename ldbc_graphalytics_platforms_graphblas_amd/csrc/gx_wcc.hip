@@ -247,46 +247,6 @@ __global__ void k_iota(int32_t *a, int64_t n) {
         a[v] = (int32_t)v;
 }
 
-// Afforest's sampling rounds (each vertex with its first, then its second neighbour), each
-// followed by pointer jumping: round 0 by k_afforest_hook0/link0, round 1 by min-hook passes
-// before the CAS links (GX_WCC_HOOK0=0 / GX_WCC_MINHOOK=0: CAS links only).
-int afforest_sample(gx_graph *g, int32_t *parent, unsigned vgrid, int rounds, hipStream_t s) {
-    gx_ctx *ctx = g->ctx;
-    const int64_t n = (int64_t)g->n;
-    // default on for undirected graphs only: on SYN-cit (directed, out-neighbours) the
-    // passes cost more than the CAS links they spare (1.21 vs 1.09 ms)
-    const bool und = !g->directed;
-    const bool hook0 = std::getenv("GX_WCC_HOOK0") ? std::atoi(std::getenv("GX_WCC_HOOK0")) != 0 : und;
-    const int minhook = std::getenv("GX_WCC_MINHOOK") ? std::atoi(std::getenv("GX_WCC_MINHOOK")) : (und ? 1 : 0);
-    for (int r = 0; r < rounds; r++) {
-        for (int pass = 0; r > 0 && pass < minhook; pass++) {
-            KTimer kt(ctx, "wcc_sample", s);
-            hipLaunchKernelGGL(k_afforest_minhook, dim3(vgrid), dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n, r,
-                               parent);
-            hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent, n);
-        }
-        {
-            KTimer kt(ctx, "wcc_sample", s);
-            if (r == 0 && hook0) {
-                hipLaunchKernelGGL(k_afforest_hook0, dim3(vgrid), dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n,
-                                   parent);
-                hipLaunchKernelGGL(k_afforest_link0, dim3(vgrid), dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n,
-                                   parent);
-            } else {
-                hipLaunchKernelGGL(k_afforest_sample, dim3(vgrid), dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n,
-                                   r, parent);
-            }
-        }
-        GX_TRY(check_launch("k_afforest_sample"));
-        {
-            KTimer kt(ctx, "wcc_compress", s);
-            hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent, n);
-        }
-        GX_TRY(check_launch("k_wcc_compress"));
-    }
-    return GX_SUCCESS;
-}
-
 // Labels of a run on the hub-first copy (gx_graph::out_perm): a component's label is its
 // smallest vertex id in the caller's numbering, the min of order[] over its members.  The
 // giant component's members (root `giant`) meet in a workgroup min first, since one word
@@ -328,40 +288,90 @@ __global__ void k_wcc_label_gather(const int32_t *__restrict__ parent, const int
     }
 }
 
-}  // namespace
-}  // namespace gx
+struct WccKnobs {
+    bool hook0;    // GX_WCC_HOOK0: round 0 by k_afforest_hook0 / link0, not CAS links
+    int minhook;   // GX_WCC_MINHOOK: min-hook passes before the CAS links of round 1
+    int rounds;    // sampling rounds, and the row entries the links after them skip
+};
 
-using namespace gx;
-
-extern "C" int gx_wcc(gx_graph *g, uint64_t *comp) {
-    if (!g || !comp) return fail(GX_NULL_POINTER, "gx_wcc: null argument");
-    gx_ctx *ctx = g->ctx;
-    GX_HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int64_t n = (int64_t)g->n, nnz = (int64_t)g->nnz;
-    if (n == 0) return GX_SUCCESS;
-    {
-        gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
-        GX_TRY(hub_for(g, ++g->wcc_calls, &h, nullptr));
-        if (h) return gx_wcc(h, comp);
-    }
-    int32_t *giant_d = nullptr;   // device word holding the giant component's root
-    DBuf<int32_t> parent;
-    GX_TRY(parent.alloc(n));
-    GX_TRY(device_begin(ctx));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, parent.p, n);
-    GX_TRY(check_launch("k_iota"));
-    const unsigned vgrid = grid_for(n, kWccBlock, 8192);
-    if (!g->directed && nnz) {
-        // ---- Afforest: sample two neighbours per vertex, find the giant component from
-        // 1024 sampled roots, then link only the remaining edges of the other vertices.  On the
-        // hub-first copy with sorted rows one round suffices: every first neighbour is the
+// The only place that reads a knob, once per call (on the graph the call runs on).
+WccKnobs wcc_knobs(const gx_graph *g) {
+    // hook0 / minhook default on for undirected graphs only: on SYN-cit (directed, out-neighbours)
+    // the passes cost more than the CAS links they spare (1.21 vs 1.09 ms)
+    const bool und = !g->directed;
+    WccKnobs k{und, und ? 1 : 0, 2};
+    if (const char *e = std::getenv("GX_WCC_HOOK0")) k.hook0 = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GX_WCC_MINHOOK")) k.minhook = std::atoi(e);
+    if (und) {
+        // on the hub-first copy with sorted rows one round suffices: every first neighbour is the
         // vertex's largest hub, so that round already joins the giant component (build_hub,
-        // gx_runtime.hip); GX_WCC_ROUNDS overrides (1 or 2).
-        int rounds = g->rows_sorted ? 1 : 2;
-        if (const char *e = std::getenv("GX_WCC_ROUNDS")) rounds = std::max(1, std::min(2, std::atoi(e)));
-        GX_TRY(afforest_sample(g, parent.p, vgrid, rounds, s));
-        // sample ids: a fixed hash sequence, uploaded once per graph size
+        // gx_runtime.hip); GX_WCC_ROUNDS overrides (1 or 2).  Directed graphs: always 2.
+        k.rounds = g->rows_sorted ? 1 : 2;
+        if (const char *e = std::getenv("GX_WCC_ROUNDS")) k.rounds = std::max(1, std::min(2, std::atoi(e)));
+    }
+    return k;
+}
+
+// One gx_wcc call and its stages, in the order the entry point runs them.
+struct WccCall {
+    gx_graph *g;
+    WccKnobs kn;
+    gx_ctx *ctx;
+    hipStream_t s;
+    int64_t n, nnz;
+    unsigned vgrid;
+    DBuf<int32_t> parent;
+    int32_t *giant_d = nullptr;   // device word holding the giant component's root
+    const int32_t *res = nullptr;
+
+    explicit WccCall(gx_graph *g_)
+        : g(g_), kn(wcc_knobs(g_)), ctx(g_->ctx), s(g_->ctx->stream), n((int64_t)g_->n), nnz((int64_t)g_->nnz),
+          vgrid(grid_for((uint64_t)g_->n, kWccBlock, 8192)) {}
+
+    int compress() {
+        {
+            KTimer kt(ctx, "wcc_compress", s);
+            hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent.p, n);
+        }
+        return check_launch("k_wcc_compress");
+    }
+
+    // Stage 1: every vertex its own tree.
+    int init() {
+        hipLaunchKernelGGL(k_iota, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, parent.p, n);
+        res = parent.p;
+        return check_launch("k_iota");
+    }
+
+    // Stage 2: Afforest's sampling rounds (each vertex with its first, then its second neighbour),
+    // each followed by pointer jumping: round 0 by k_afforest_hook0/link0, round 1 by min-hook
+    // passes before the CAS links (GX_WCC_HOOK0=0 / GX_WCC_MINHOOK=0: CAS links only).
+    int sample() {
+        const int64_t *rp = g->A.rp.p;
+        const int32_t *ci = g->A.ci.p;
+        for (int r = 0; r < kn.rounds; r++) {
+            for (int pass = 0; r > 0 && pass < kn.minhook; pass++) {
+                KTimer kt(ctx, "wcc_sample", s);
+                hipLaunchKernelGGL(k_afforest_minhook, dim3(vgrid), dim3(kWccBlock), 0, s, rp, ci, n, r, parent.p);
+                hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent.p, n);
+            }
+            {
+                KTimer kt(ctx, "wcc_sample", s);
+                if (r == 0 && kn.hook0) {
+                    hipLaunchKernelGGL(k_afforest_hook0, dim3(vgrid), dim3(kWccBlock), 0, s, rp, ci, n, parent.p);
+                    hipLaunchKernelGGL(k_afforest_link0, dim3(vgrid), dim3(kWccBlock), 0, s, rp, ci, n, parent.p);
+                } else {
+                    hipLaunchKernelGGL(k_afforest_sample, dim3(vgrid), dim3(kWccBlock), 0, s, rp, ci, n, r, parent.p);
+                }
+            }
+            GX_TRY(check_launch("k_afforest_sample"));
+            GX_TRY(compress());
+        }
+        return GX_SUCCESS;
+    }
+
+    // The sample ids of k_pick_giant: a fixed hash sequence, uploaded once per graph size.
+    int sample_ids() {
         if (!g->wcc_ids.p || g->wcc_ids_n != n) {
             std::vector<int32_t> ids(kSamples);
             uint64_t h = 0x9E3779B97F4A7C15ull;
@@ -376,38 +386,36 @@ extern "C" int gx_wcc(gx_graph *g, uint64_t *comp) {
             g->wcc_ids_n = n;
         }
         giant_d = g->wcc_ids.p + kSamples;
-        hipLaunchKernelGGL(k_pick_giant, dim3(1), dim3(kSamples), 0, s, parent.p, g->wcc_ids.p, giant_d);
-        GX_TRY(check_launch("k_pick_giant"));
+        return GX_SUCCESS;
+    }
+
+    // Stage 3: the entries the rounds did not sample (row positions >= kn.rounds).  Undirected:
+    // the giant component from 1024 sampled roots, then only the rows of the vertices outside it;
+    // directed: every remaining entry.  Then pointer jumping until every vertex points at its root.
+    int link() {
+        if (!g->directed) {
+            GX_TRY(sample_ids());
+            hipLaunchKernelGGL(k_pick_giant, dim3(1), dim3(kSamples), 0, s, parent.p, g->wcc_ids.p, giant_d);
+            GX_TRY(check_launch("k_pick_giant"));
+        }
         {
             KTimer kt(ctx, "wcc_hook", s);
-            hipLaunchKernelGGL(k_afforest_finish, dim3(grid_for((uint64_t)n, kWccBlock, 8192)),
-                               dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n, rounds, giant_d, parent.p);
+            if (!g->directed)
+                hipLaunchKernelGGL(k_afforest_finish, dim3(grid_for((uint64_t)n, kWccBlock, 8192)), dim3(kWccBlock), 0,
+                                   s, g->A.rp.p, g->A.ci.p, n, kn.rounds, giant_d, parent.p);
+            else
+                hipLaunchKernelGGL(k_wcc_link_edges,
+                                   dim3(grid_for((uint64_t)((nnz + kWccEdgesPerThread - 1) / kWccEdgesPerThread),
+                                                 kWccBlock, 1u << 30)),
+                                   dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n, nnz, kn.rounds, parent.p);
         }
-        GX_TRY(check_launch("k_afforest_finish"));
-        {
-            KTimer kt(ctx, "wcc_compress", s);
-            hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent.p, n);
-        }
-        GX_TRY(check_launch("k_wcc_compress"));
+        GX_TRY(check_launch(g->directed ? "k_wcc_link_edges" : "k_afforest_finish"));
+        return compress();
     }
-    if (g->directed && nnz) {
-        GX_TRY(afforest_sample(g, parent.p, vgrid, 2, s));
-        {
-            KTimer kt(ctx, "wcc_hook", s);
-            hipLaunchKernelGGL(k_wcc_link_edges,
-                               dim3(grid_for((uint64_t)((nnz + kWccEdgesPerThread - 1) / kWccEdgesPerThread),
-                                             kWccBlock, 1u << 30)),
-                               dim3(kWccBlock), 0, s, g->A.rp.p, g->A.ci.p, n, nnz, 2, parent.p);
-        }
-        GX_TRY(check_launch("k_wcc_link_edges"));
-        {
-            KTimer kt(ctx, "wcc_compress", s);
-            hipLaunchKernelGGL(k_wcc_compress, dim3(vgrid), dim3(kWccBlock), 0, s, parent.p, n);
-        }
-        GX_TRY(check_launch("k_wcc_compress"));
-    }
-    const int32_t *res = parent.p;
-    if (g->out_perm) {
+
+    // Stage 4, on the hub-first copy only: the labels in the caller's numbering.
+    int relabel() {
+        if (!g->out_perm) return GX_SUCCESS;
         int32_t *minorig = reinterpret_cast<int32_t *>(g->remap_tmp.p), *lab = minorig + n;   // 2n int32
         const int64_t live = g->live;   // roots of components with edges are below it
         if (live) {
@@ -417,11 +425,37 @@ extern "C" int gx_wcc(gx_graph *g, uint64_t *comp) {
         }
         hipLaunchKernelGGL(k_wcc_label_gather, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, parent.p, g->out_perm,
                            minorig, n, live, lab);
-        GX_TRY(check_launch("k_wcc_label_gather"));
         res = lab;
+        return check_launch("k_wcc_label_gather");
     }
+};
+
+}  // namespace
+}  // namespace gx
+
+using namespace gx;
+
+extern "C" int gx_wcc(gx_graph *g, uint64_t *comp) {
+    if (!g || !comp) return fail(GX_NULL_POINTER, "gx_wcc: null argument");
+    gx_ctx *ctx = g->ctx;
+    GX_HIP_TRY(hipSetDevice(ctx->device));
+    if (g->n == 0) return GX_SUCCESS;
+    {
+        gx_graph *h = nullptr;   // hub-first copy from the second call (gx_runtime.hip hub_for)
+        GX_TRY(hub_for(g, ++g->wcc_calls, &h, nullptr));
+        if (h) return gx_wcc(h, comp);
+    }
+    WccCall c(g);
+    GX_TRY(c.parent.alloc(c.n));
+    GX_TRY(device_begin(ctx));
+    GX_TRY(c.init());
+    if (c.nnz) {
+        GX_TRY(c.sample());
+        GX_TRY(c.link());
+    }
+    GX_TRY(c.relabel());
     GX_TRY(device_end(ctx));
-    GX_TRY(download(ctx, comp, res, (uint64_t)n, Xfer::Widen32));
+    GX_TRY(download(ctx, comp, c.res, (uint64_t)c.n, Xfer::Widen32));
     return GX_SUCCESS;
 }
 

@@ -24,7 +24,7 @@ from oracle import oracle as O
 
 KNOBS = {"GX_LCC_WAVE_MAX": "8", "GX_LCC_WAVE2_MAX": "24", "GX_LCC_BLOCK_MAX": "48"}
 KNOB_LIMITS = (8, 24, 48)
-DEFAULT_LIMITS = (256, 512, 8192)   # kWaveMax, kWave2Max, kBlockMax of gx_lcc.hip
+DEFAULT_LIMITS = (256, 512, 8192)   # kWaveMax, kWave2Max, kBlockMax of gx_lcc.h
 TIMERS = ("lcc_wave", "lcc_wave2", "lcc_block", "lcc_merge")
 KNOB_SEED = 51   # chosen so that the 128th and 129th largest closure degrees differ (_knob_case)
 FP64_MAX_N = 1500
@@ -78,7 +78,7 @@ def _dense_lcc(csr, verts=None):
 
 def _oriented(S):
     """(|O(u)|, |I(u)|, rank key): neighbours ranking above / below u by (degree, id), the
-    orientation of ranks_above in gx_lcc.hip."""
+    orientation of ranks_above in gx_lcc_orient.hip."""
     n = S.shape[0]
     deg = S.sum(1, dtype=np.float64).astype(np.int64)
     key = deg * n + np.arange(n)
@@ -137,7 +137,7 @@ def _knob_case(directed):
     # without the knobs: the wave tiers only
     t0 = _tiers(d, e, DEFAULT_LIMITS)
     assert (t0 == 0).any() and (t0 == 1).any() and not (t0 >= 2).any()
-    # the dense core at GX_LCC_CORE=128 (lcc_core_build): degrees above the 129th largest
+    # the dense core at GX_LCC_CORE=128 (lcc_dense_build): degrees above the 129th largest
     deg = S.sum(1).astype(np.int64)
     top = np.sort(deg)[::-1]
     assert top[127] > top[128], "the degree cut must leave a core of exactly 128"
